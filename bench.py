@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fwd+bwd throughput of the TT-EmbeddingBag hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one forward + backward (fused SGD) of the module over one batch of
@@ -22,11 +22,17 @@ default workload (cfg2)
 
 value = true algorithmic GFLOP/s = 3 * 2*(q0 r1 q1 r2 + q0 q1 r2 q2) * nnz / time (the reference's formula,
 :154-158/:190, WITHOUT its x iters slip; the README's 2657.6 "GFLOPS" is 265.8 on this scale -- BASELINE.md).
-The timed region of K steps is repeated --repeats times; `value` / `ms_per_step` are the MEDIAN region,
-`spread` holds min / max.  ONE JSON line by rank 0, with the roofline of the dominant kernel (backward
-contraction, timed live with HIP events on its stream; `traffic` from the rocprofv3 PMC passes of
-scripts/measure_traffic.sh if they were taken on THIS build) and a CPU baseline (oracle/ttx_cpu_baseline.c on
-all host cores, bounded sample).
+The timed region of K steps is repeated --repeats times (default 1; 5 with --full); `value` / `ms_per_step` are
+the MEDIAN region, `spread` holds min / max.  ONE JSON line by rank 0, with the roofline of the dominant kernel
+(backward contraction, timed live with HIP events captured in the replayed graph; `traffic` from the rocprofv3 PMC
+passes of scripts/measure_traffic.sh if they were taken on THIS build).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every other measurement in the
+same line: the eager figures, the replay without planning ahead (`no_prefetch`), the per-kernel HIP-event breakdown
+(`kernel_us`), a CPU baseline (oracle/ttx_cpu_baseline.c on all host cores, bounded sample), the default workload's
+`secondary` records and nn.EmbeddingBag baseline, and with N > 1 the all-to-all figures and the one-GPU `n1` record.
+--dump-outputs DIR writes what the timed path computed in its last step (forward output, updated TT cores) as
+DIR/<name>.npy.
 """
 import argparse
 import glob
@@ -55,6 +61,11 @@ import torch.distributed as dist  # noqa: E402
 
 P_SHAPES = [200, 220, 250]
 POOL = 20
+# The fused optimizer's learning rate.  Every step applies the same d_output to the same ten request batches -- a linear loss with no
+# minimum -- so the cores only ever grow: at 0.1 they overflowed to inf / NaN within about a dozen steps and every later step computed
+# on NaNs.  At 1e-6 they stay finite for hundreds of thousands of steps while each update still moves them (relative 1e-5 per step),
+# so --dump-outputs holds numbers two builds can be compared on.  The kernels' work does not depend on it.
+LEARNING_RATE = 1e-6
 PEAK_FP32_TFLOPS = 157.3  # MI355X fp32 MFMA/VALU dense peak (MI355X_MICROARCH.md)
 PEAK_HBM_TBS = 8.0        # HBM3E spec (6.3 TB/s achievable), same guide
 XGMI_GBS = 153.0          # per link, per direction
@@ -224,7 +235,7 @@ def secondary_record(workload="cfg5shard", steps=40, repeats=3):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(steps), "--warmup", "10", "--repeats",
-           str(repeats), "--no-cpu-baseline", "--no-secondary"]
+           str(repeats), "--full", "--no-cpu-baseline", "--no-secondary"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -265,6 +276,26 @@ def predict_cfg5_8gpu(shard_ms, exchange_latency_us=20.0):
                        "time; the rest is a guess until two devices have talked), transfers at the 153 GB/s link rate, no overlap "
                        "of an exchange with the local lookup, the busiest owner (4 of 26 tables) sets the pace",
             "ideal_speedup_over_one_gpu": round(NT / own, 2)}
+
+
+DUMP_MAX_ELEMS = 1 << 21  # --dump-outputs: per array, 8 MB of float32 (at most five arrays: the output and four cores)
+DUMP_SEED = 20240607      # ... larger arrays are written as this fixed sample of their flattened elements
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32; one holding more than DUMP_MAX_ELEMS elements is written as a
+    fixed, seeded sample of its flattened elements (the same positions on every run of the same arguments)"""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        total += a.nbytes
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (more than 64 MB)"
+    print(f"[bench] outputs of the last timed step: {', '.join(arrays)} -> {dirname}", file=sys.stderr, flush=True)
 
 
 def self_launch(n):
@@ -318,7 +349,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline figure: eager figures, no_prefetch, per-kernel breakdown, CPU "
+                         "baseline, the default workload's secondary records and dense baseline, N > 1 all-to-all and n1 record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (forward output, TT cores "
+                         "after its fused optimizer update) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cache", action="store_true", help="use_cache=False (skip the hash-table frequency update)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="time the eager Python path only (no hipGraph replay)")
@@ -337,6 +375,8 @@ def main():
     ap.add_argument("--no-n1", action="store_true",
                     help="N > 1: skip rank 0's one-GPU run of the same workload (the `n1` record of the line)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started by itself: spawn the ranks (the driver's `python bench.py --gpus N` and its torch.distributed.run form both work)
         sys.exit(self_launch(args.gpus))
@@ -399,9 +439,15 @@ def main():
     B_local = B_GLOBAL // world
     torch.manual_seed(1234 + rank)
     reqs_np = cores_np = d_out_np = None
+    outs = {}  # --dump-outputs: address of a batch's indices -> the output of the latest step (run or captured) on that batch
+
+    def fwd_bwd(out, idx):
+        if args.dump_outputs:
+            outs[idx.data_ptr()] = out  # (kept alive: a captured step's output is rewritten by every replay)
+        out.backward(grad)
     if not sharded:
         use_cache = (not args.no_cache) and ntab == 1
-        kw = dict(sparse=True, optimizer=opt, learning_rate=0.1, use_cache=use_cache, weight_dist="uniform", device=dev,
+        kw = dict(sparse=True, optimizer=opt, learning_rate=LEARNING_RATE, use_cache=use_cache, weight_dist="uniform", device=dev,
                   dedup=bool(wl.get("dedup", False)))
         if wl["populate"]:  # cfg3: 256Ki-row cache behind a 1Mi-slot table
             kw.update(cache_size=1 << 18, hashtbl_size=1 << 20)
@@ -417,7 +463,7 @@ def main():
         reqs = [(torch.from_numpy(i).to(dev), torch.from_numpy(o).to(dev)) for i, o in reqs_np]
         d_out_np = G.make_grad(1236, ntab, B_GLOBAL, D)
         grad = torch.from_numpy(d_out_np[0] if ntab == 1 else d_out_np).to(dev)
-        step = lambda i, o: mod(i, o).backward(grad)  # noqa: E731
+        step = lambda i, o: fwd_bwd(mod(i, o), i)  # noqa: E731
         nnz_step_total = ntab * B_GLOBAL * POOL
         tables_total, owned = ntab, [ntab]
         if wl["populate"]:
@@ -435,12 +481,12 @@ def main():
         tables_total = ntab if cfg5 else world
         mod = ttx_sharded.ShardedTableBatchedTTEmbeddingBag(
             tables_total, E_, D, RANKS, tt_p_shapes=P_SHAPES, tt_q_shapes=Q_SHAPES, sparse=True, optimizer=opt,
-            learning_rate=0.1, use_cache=False, weight_dist="uniform", device=dev)
+            learning_rate=LEARNING_RATE, use_cache=False, weight_dist="uniform", device=dev)
         owned = [len(o) for o in mod.owned]
         reqs_np = G.make_requests(1235 + rank, iters, B_local, tables_total, POOL, E_)
         reqs = [(torch.from_numpy(i).to(dev), torch.from_numpy(o).to(dev)) for i, o in reqs_np]
         grad = torch.from_numpy(G.make_grad(1236 + rank, tables_total, B_local, D)).to(dev)
-        step = lambda i, o: mod(i, o, fixed_pooling=POOL).backward(grad)  # noqa: E731
+        step = lambda i, o: fwd_bwd(mod(i, o, fixed_pooling=POOL), i)  # noqa: E731
         nnz_step_total = tables_total * B_GLOBAL * POOL  # every table sees the whole global batch
 
     rank_regions = []  # sharded: per timed region, every rank's elapsed seconds
@@ -472,24 +518,27 @@ def main():
     eager_steps(args.warmup)
     sync()
 
-    # ---- region 1 (eager Python path): live HIP-event timing of the dominant kernel ----
-    E.profile_reset()
-    E.profile_enable(1 << E.PROF_BWD)
-    eager_elapsed = timed(eager_steps, args.steps)
-    E.profile_enable(0)
-    n_bwd, ms_bwd = E.profile_read(E.PROF_BWD)
-    bwd_src = "HIP events around each launch of the eager region"
-    # ... and the same loop with no event brackets in the stream: THE eager figure (`eager_ms_per_step`).  A timing event pair per
-    # launch costs the stream ~2 x 10 us of marker packets -- the bracketed region above ran at about half this one's rate and was
-    # what rounds 1-4 (and this round's first lines) reported as the eager step.
-    eager_profiled = eager_elapsed
-    eager_elapsed = timed(eager_steps, args.steps)
-    eager_regions = [eager_elapsed]
+    # ---- region 1 (eager Python path, --full): live HIP-event timing of the dominant kernel ----
+    n_bwd, ms_bwd, bwd_src = 0, 0.0, "no HIP events (the eager regions are timed with --full)"
+    eager_profiled = eager_elapsed = eager_direct = None
+    eager_regions = []
+    if args.full:
+        E.profile_reset()
+        E.profile_enable(1 << E.PROF_BWD)
+        eager_elapsed = timed(eager_steps, args.steps)
+        E.profile_enable(0)
+        n_bwd, ms_bwd = E.profile_read(E.PROF_BWD)
+        bwd_src = "HIP events around each launch of the eager region"
+        # ... and the same loop with no event brackets in the stream: THE eager figure (`eager_ms_per_step`).  A timing event pair per
+        # launch costs the stream ~2 x 10 us of marker packets -- the bracketed region above ran at about half this one's rate and was
+        # what rounds 1-4 (and this round's first lines) reported as the eager step.
+        eager_profiled = eager_elapsed
+        eager_elapsed = timed(eager_steps, args.steps)
+        eager_regions = [eager_elapsed]
     # ... and once more with the OPT-IN direct backward (round 6: importing the module no longer wraps torch.Tensor.backward;
     # ops.enable_direct_backward() does, explicitly): `out.backward(grad)` of the lookup's own output calls its node on the
     # calling thread instead of going through autograd's engine.  Reported beside the plain figure, never instead of it.
-    eager_direct = None
-    if not sharded and hasattr(ops, "enable_direct_backward"):
+    if args.full and not sharded and hasattr(ops, "enable_direct_backward"):
         ops.enable_direct_backward()
         try:
             eager_steps(min(args.warmup, 10))
@@ -611,21 +660,10 @@ def main():
                             {"ms_per_step": round(statistics.median(plain_regions) / args.steps * 1e3, 4),
                              "value": round(3.0 * fl_fwd * nnz_step_total / (statistics.median(plain_regions) / args.steps) / 1e9, 2),
                              "what": "the same captured round with every step's prologue in line (no side stream)"}),
-            "eager_ms_per_step": round(eager_elapsed / args.steps * 1e3, 4),
-            "eager_value": round(3.0 * fl_fwd * nnz_step_total / (eager_elapsed / args.steps) / 1e9, 2),
-            "eager_what": ("the reference benchmark's loop form, `tt_emb(indices, offsets).backward(grad)` per request "
-                           "(tt_embeddings_benchmark.py:94-108), free-running, no graph, no planning ahead, no event brackets, "
-                           "backward() through autograd's engine (the module as imported)"),
             "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
-            "eager_with_event_brackets_ms_per_step": round(eager_profiled / args.steps * 1e3, 4),
-            "eager_direct_backward": (None if eager_direct is None else {
-                "ms_per_step": round(eager_direct / args.steps * 1e3, 4),
-                "what": "the same loop after ops.enable_direct_backward() (opt-in, off by default: wraps torch.Tensor.backward so "
-                        "that backward() of a fused-optimizer lookup's own output skips autograd's engine)"}),
             "us_per_nnz": round(elapsed / args.steps / nnz_step_total * 1e6, 5),
             "ref_formula_gflops_x_iters": round(gflops * 10, 1),
             "reference_readme_true_gflops": 265.8,
-            "kernel_us": breakdown,
             # ONE figure per kernel (round 5): `achieved` / `frac` divide the algorithmic FLOP of a launch by the kernel's average
             # duration as rocprofv3 --kernel-trace --stats reports it for THIS build (profiles/, reproducible by hand from
             # <tag>_kernel_stats*.md); the live HIP-event bracket of this run -- which includes event overhead and, in an eager
@@ -644,9 +682,23 @@ def main():
                 "flop_per_launch": bwd_flop_per_launch, "lookups_per_launch": round(launch_nnz, 1),
                 "kernel_build": source_hash()})(
                     (bwd_flop_per_launch / (rocprof_us * 1e-6) / 1e12) if rocprof_us else None),
-            "kernel_us_note": ("HIP-event brackets around each launch in an eager pass: every bracket includes ~2 us of launch "
-                               "gap, so their sum exceeds the replayed step; rocprofv3 durations: profiles/"),
         }
+        if eager_elapsed is not None:
+            line.update({
+                "eager_ms_per_step": round(eager_elapsed / args.steps * 1e3, 4),
+                "eager_value": round(3.0 * fl_fwd * nnz_step_total / (eager_elapsed / args.steps) / 1e9, 2),
+                "eager_what": ("the reference benchmark's loop form, `tt_emb(indices, offsets).backward(grad)` per request "
+                               "(tt_embeddings_benchmark.py:94-108), free-running, no graph, no planning ahead, no event brackets, "
+                               "backward() through autograd's engine (the module as imported)"),
+                "eager_with_event_brackets_ms_per_step": round(eager_profiled / args.steps * 1e3, 4),
+                "eager_direct_backward": (None if eager_direct is None else {
+                    "ms_per_step": round(eager_direct / args.steps * 1e3, 4),
+                    "what": "the same loop after ops.enable_direct_backward() (opt-in, off by default: wraps torch.Tensor.backward so "
+                            "that backward() of a fused-optimizer lookup's own output skips autograd's engine)"})})
+        if args.full:
+            line["kernel_us"] = breakdown
+            line["kernel_us_note"] = ("HIP-event brackets around each launch in an eager pass: every bracket includes ~2 us of launch "
+                                      "gap, so their sum exceeds the replayed step; rocprofv3 durations: profiles/")
         if len(Q_SHAPES) == 2 and n_bwd:
             # two cores: a lookup is one [q0 x r1] x [r1 x q1] product -- 2 FLOP per byte fetched: the bound is bandwidth, not the
             # matrix pipe.  Algorithmic bytes of the backward per lookup: core-0 slice read + its partial row written (q0 r1 floats
@@ -708,6 +760,18 @@ def main():
     # (ttx_sharded.DirectExchange: current stream, capturable; torch.distributed's own collectives are not).
     # Falls back to the eager timing if capture is unavailable.
     mode, regions, plain_regions = "eager", None, None
+    last_outputs = None  # --dump-outputs: snapshot_outputs() right after the reported timed regions
+
+    def snapshot_outputs():
+        """what the timed path computed in its last step (batch (K - 1) % 10): the forward output a caller receives and the TT
+        cores as that step's fused optimizer update left them, as float32 host arrays"""
+        sync()
+        arrays = {"output": outs[reqs[(args.steps - 1) % iters][0].data_ptr()]}
+        owner = mod.local if sharded else mod
+        for t, c in enumerate(owner.tt_cores if owner is not None else []):
+            arrays[f"core{t}"] = c
+        return {name: a.detach().float().cpu().numpy() for name, a in arrays.items()}
+
     degraded = None  # set when the reported mode is a fallback: the line says so and a multi-GPU run exits non-zero
     can_graph = not args.no_graph and (not wl["populate"] or ops._native_node() is not None)
     if sharded:
@@ -721,7 +785,7 @@ def main():
                 import threading
 
                 def bail():  # a hung collective must not take the driver's slot with it -- and must not look like success
-                    if rank == 0:
+                    if rank == 0 and eager_regions:  # (the eager regions are timed with --full only)
                         line = build_line("eager", eager_regions, {}, None,
                                           note="direct-RCCL graph region did not finish; eager torch.distributed result")
                         line["degraded"] = "watchdog: the captured direct-RCCL region hung; exit code 3"
@@ -768,12 +832,16 @@ def main():
                     mod._prefetched.clear()
             if pipelined:
                 mk = ttx_graph.planned_round if args.prefetch == "round" else ttx_graph.pipelined_round
-                round_fn = mk(mod, reqs, lambda out, k: out.backward(grad), **pf_kw)
+                round_fn = mk(mod, reqs, lambda out, k: fwd_bwd(out, reqs[k][0]), **pf_kw)
             E.profile_reset()
             E.profile_mask(1 << E.PROF_BWD)  # the event pairs around the backward kernel become graph nodes
             g_round = ttx_graph.GraphedRound(round_fn, [()], warmup=3) if pipelined else ttx_graph.GraphedRound(step, reqs, warmup=3)
             E.profile_mask(0)
-            singles = [ttx_graph.GraphedRound(step, [b], warmup=0) for b in reqs[:args.steps % iters]]
+            # replays before the timed region: at least 500 steps -- the first ~200 replayed steps run ~2 % slower than every later
+            # region (measured at cfg2), a single timed region must not carry that
+            graph_warmup = max(args.warmup, iters, 500)
+            # (single-step graphs for the remainder of the warm-up as well as of the timed steps)
+            singles = [ttx_graph.GraphedRound(step, [b], warmup=0) for b in reqs[:max(args.steps % iters, graph_warmup % iters)]]
 
             def graph_steps(n):
                 for _ in range(n // iters):
@@ -783,12 +851,14 @@ def main():
 
             if dog is not None:
                 dog.start()
-            graph_steps(max(args.warmup, iters))
+            graph_steps(graph_warmup)
             regions = [timed(graph_steps, args.steps) for _ in range(max(1, args.repeats))]
             reported_ranks[:] = rank_regions[-1] if rank_regions else []
+            if args.dump_outputs:
+                last_outputs = snapshot_outputs()
             mode = (("hipgraph+direct-rccl" + ("+prefetch-round" if pipelined else "")) if sharded
                     else (f"hipgraph+prefetch-{args.prefetch}" if pipelined else "hipgraph"))
-            if pipelined:  # the same round without the overlap, for the record
+            if pipelined and args.full:  # the same round without the overlap, for the record
                 g_plain = ttx_graph.GraphedRound(step, reqs, warmup=1)
                 pipelined_round_replay, g_round = g_round, g_plain
                 graph_steps(iters)
@@ -811,19 +881,24 @@ def main():
                 if hasattr(mod, "drop_planned"):
                     mod.drop_planned()
             regions = None
+            last_outputs = None
             torch.cuda.synchronize()
         finally:
             if dog is not None:
                 dog.cancel()
     if regions is None:  # eager is the reported mode: repeat it like the graph region
-        eager_regions += [timed(eager_steps, args.steps) for _ in range(max(0, args.repeats - 1))]
+        eager_regions += [timed(eager_steps, args.steps) for _ in range(max(1, args.repeats) - len(eager_regions))]
         regions = eager_regions
         reported_ranks[:] = rank_regions[-1] if rank_regions else []
+        if args.dump_outputs:
+            last_outputs = snapshot_outputs()
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, last_outputs)
 
     # N > 1: the two exchanges of a step in isolation (xGMI all-to-all bandwidth vs the link roofline), with the
     # step's own per-peer message sizes (uneven when the tables do not divide by the ranks)
     a2a = None
-    if sharded:
+    if sharded and args.full:
         try:
             a2a = {}
             n_me = owned[rank]
@@ -854,19 +929,20 @@ def main():
         except Exception as ex:  # noqa: BLE001
             a2a = {"error": f"{type(ex).__name__}: {ex}"}
 
-    # second, untimed pass: per-kernel breakdown (all kernel slots bracketed)
-    E.profile_reset()
-    E.profile_enable(0x3F)
-    eager_steps(min(args.steps, 50))
-    sync()
-    E.profile_enable(0)
-    names = ["fwd_contract", "bwd_contract", "reduce_apply", "plan", "bag_pool", "cache_gather"]
+    # second, untimed pass (--full): per-kernel breakdown (all kernel slots bracketed)
     breakdown, launches = {}, {}
-    for w, nm in enumerate(names):
-        n, ms = E.profile_read(w)
-        if n:
-            breakdown[nm + "_us"] = round(ms / n * 1e3, 2)
-            launches[nm] = n
+    if args.full:
+        E.profile_reset()
+        E.profile_enable(0x3F)
+        eager_steps(min(args.steps, 50))
+        sync()
+        E.profile_enable(0)
+        names = ["fwd_contract", "bwd_contract", "reduce_apply", "plan", "bag_pool", "cache_gather"]
+        for w, nm in enumerate(names):
+            n, ms = E.profile_read(w)
+            if n:
+                breakdown[nm + "_us"] = round(ms / n * 1e3, 2)
+                launches[nm] = n
 
     if rank == 0:
         line = build_line(mode, regions, breakdown, a2a)
@@ -907,13 +983,13 @@ def main():
                 line["cache_gather_roofline"]["rocprof_avg_us"] = None
         if hit_rate is not None:
             line["cache_hit_rate"] = round(hit_rate, 4)
-        if not sharded and not args.no_cpu_baseline and ntab == 1:
+        if args.full and not sharded and not args.no_cpu_baseline and ntab == 1:
             line["cpu_baseline"] = cpu_baseline(reqs_np, cores_np, d_out_np, Q_SHAPES, RANKS, B_GLOBAL)
         if args.run_baseline and not sharded and ntab == 1:
             line["dense_embedding_bag"] = dense_baseline(E_, D, reqs, grad, args.steps, args.warmup)
         if degraded:
             line["degraded"] = degraded
-        if args.workload == "cfg2" and not sharded and not args.no_secondary:
+        if args.full and args.workload == "cfg2" and not sharded and not args.no_secondary:
             # (round 6) every BASELINE.json config under the driver's clock: besides the default line's configs[1], one rank's
             # share of configs[4] (the regime where the contraction kernels are the bound), configs[3] (fused Adagrad at ranks 64,
             # D = 128: its own roofline) and configs[2] (the row cache live on a Zipf stream: hit rate, cache_gather_roofline).
@@ -968,7 +1044,7 @@ def main():
             # N > 1: the ONE line is printed here, after the communicators are gone and the other ranks have left rank 0's GPU alone,
             # with the one-GPU value of the same workload beside it (the driver computes the scaling efficiency itself; this is the
             # same-box, same-job denominator for anyone reading the line alone)
-            if not args.no_n1:
+            if args.full and not args.no_n1:
                 line["n1"] = n1_record(args.workload, args.steps, args.warmup, local_rank)
                 if "value" in line["n1"] and line["n1"]["value"] > 0:
                     # weak scaling: per-GPU work fixed -> ideal = N x n1; strong: total work fixed -> ideal = N x n1 as well (value is the

@@ -8,4 +8,4 @@ TTX_NO_NATIVE_NODE=1 scripts/kprof.sh khead$rep $W > /dev/null 2>&1
 done
 for t in nokhead1 khead1 nokhead2 khead2; do echo "== $t"; cat gpurun_out/kprof_$t/$W.md; done
 scripts/cmp_variants.sh "--workload $W --steps 200 --warmup 20 --no-secondary" nokhead
-TTX_NO_NATIVE_NODE=1 python bench.py --workload $W --steps 200 --warmup 20 --no-secondary --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('khead', d['value'], d['ms_per_step'], d['kernel_us'])"
+TTX_NO_NATIVE_NODE=1 python bench.py --full --workload $W --steps 200 --warmup 20 --no-secondary --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('khead', d['value'], d['ms_per_step'], d['kernel_us'])"

@@ -38,8 +38,8 @@ cp gpurun_out/kprof_$TAG/rocprof_kernels.json profiles/ 2>/dev/null   # (on the 
 scripts/cache_rocprof.sh "$TAG" > /dev/null 2>&1
 cp gpurun_out/cache_prof_$TAG/summary.md "$OUT/${TAG}_cache_bandwidth.md" 2>/dev/null
 fi
-python bench.py --steps 200 --repeats 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+python bench.py --full --steps 200 --repeats 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 for W in $BENCH_W; do
-  python bench.py --workload $W --steps 100 --repeats 3 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$W.json"
+  python bench.py --full --workload $W --steps 100 --repeats 3 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$W.json"
 done
 ls -la "$OUT"

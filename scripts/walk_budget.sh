@@ -1,6 +1,6 @@
 for b in 163840 122880 98304 81920 65536 49152; do
 for w in r128; do
-TTX_LDS_BUDGET=$b python bench.py --workload $w --steps 20 --repeats 2 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+TTX_LDS_BUDGET=$b python bench.py --full --workload $w --steps 20 --repeats 2 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$w budget $b', d['ms_per_step'], d['kernel_us'])"
 done; done
 python - <<'PY'

@@ -18,7 +18,9 @@ def pytest_configure(config):
 def _load_cases(fname):
     import numpy as np
 
-    z = np.load(os.path.join(HERE, "golden", fname))
+    from util import load_golden
+
+    z = load_golden(os.path.join(HERE, "golden", fname))
     names = sorted({k.split("/")[0] for k in z.files})
     cases = {}
     for name in names:

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import gen_inputs as G  # noqa: E402
+from util import save_golden  # noqa: E402  (parts of at most 1000 KiB: tests/golden/<name>-<k>.npz)
 
 sys.modules.setdefault("tt_embeddings", types.ModuleType("tt_embeddings"))
 sys.path.insert(0, "/root/reference")
@@ -131,7 +132,7 @@ def write_small(cases=None, fname="small_cases.npz"):
             blob[f"{name}/core{t}"] = cores[t]
             blob[f"{name}/grad{t}"] = grads[t]
         print(name, "nnz", idx.size, "out", out.shape)
-    np.savez_compressed(os.path.join(HERE, fname), **blob)
+    save_golden(os.path.join(HERE, fname), blob)
 
 
 def write_big(tag, cfg, seed, nrows=16):
@@ -152,7 +153,7 @@ def write_big(tag, cfg, seed, nrows=16):
         blob[f"ada{t}_sub"] = ada[t].reshape(g.shape)[rows]
         blob[f"grad{t}_sum"] = np.array([g.astype(np.float64).sum(), (g.astype(np.float64) ** 2).sum()])
         blob[f"grad{t}_rowsum"] = g.astype(np.float64).sum(axis=1)  # per-slice sums (p_t doubles)
-    np.savez_compressed(os.path.join(HERE, f"{tag}.npz"), **blob)
+    save_golden(os.path.join(HERE, f"{tag}.npz"), blob)
     print(tag, "out", out.shape, [float(blob[f"grad{t}_sum"][0]) for t in range(3)])
 
 
@@ -175,7 +176,7 @@ def write_cfg5():
             blob[f"t{k}_sgd{t}_sub"] = sgd[t].reshape(g.shape)[rows]
             blob[f"t{k}_grad{t}_rowsum"] = g.astype(np.float64).sum(axis=1)
         print("cfg5 table", k, "out", out.shape)
-    np.savez_compressed(os.path.join(HERE, "cfg5.npz"), **blob)
+    save_golden(os.path.join(HERE, "cfg5.npz"), blob)
 
 
 if __name__ == "__main__":

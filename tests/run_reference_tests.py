@@ -1,8 +1,8 @@
 """Run the REFERENCE's own property tests (/root/reference/tt_embeddings_test.py:62-525) on top of the CPU oracle.
 
-TEST INFRASTRUCTURE, BUILD CONTAINER ONLY: needs /root/reference (absent on the GPU box) and is started as a process of its own by
-tests/test_reference_own_tests.py (the reference's Python module is called `tt_embeddings_ops` like the product's; the two must not
-meet in one interpreter).  Nothing of the reference is copied: its test file and its tt_embeddings_ops.py are imported from where
+TEST INFRASTRUCTURE, run by hand where the reference tree lies (TTX_REFERENCE_DIR), as a process of its own (the reference's Python
+module is called `tt_embeddings_ops` like the product's; the two must not meet in one interpreter); `--trace` records the fixtures
+tests/test_reference_own_tests.py compares with (tests/golden/ref_cache_life_cycle.*).  Nothing of the reference is copied: its test file and its tt_embeddings_ops.py are imported from where
 they lie.  What is swapped in:
   * `tt_embeddings` (the reference's native CUDA extension, unbuildable here)  ->  tests/oracle_engine.py, the 11-function surface
     backed by oracle/ttx_oracle.c;

@@ -40,7 +40,7 @@ def test_sharded_code_path_runs_as_a_subprocess_and_prints_one_line():
     env = _env()
     env.setdefault("TTX_DIRECT_TIMEOUT", "200")
     out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--force-sharded", "--steps", "4", "--warmup", "2", "--repeats", "1",
-                          "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
+                          "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-1500:], out.stderr[-3000:])
     j = json.loads(lines[0])
@@ -50,6 +50,32 @@ def test_sharded_code_path_runs_as_a_subprocess_and_prints_one_line():
     a2a = j["all_to_all"]
     assert "error" not in a2a and a2a["pooled_out"]["us"] > 0 and "frac_of_xgmi" in a2a["indices_in"]
     assert j["per_rank_ms_per_step"] and len(j["per_rank_ms_per_step"]) == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: exactly K timed steps (one region), the headline fields only -- the other
+    measurements are --full's -- and with --dump-outputs DIR the last timed step's forward output and updated cores as .npy files"""
+    import numpy as np
+
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=600, env=_env())
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-1500:], out.stderr[-3000:])
+    j = json.loads(lines[0])
+    assert j["steps"] == 7 and j["repeats"] == 1 and len(j["spread"]["region_ms"]) == 1
+    assert j["timed_mode"].startswith("hipgraph") and "degraded" not in j, j.get("degraded")
+    assert j["value"] > 0 and j["unit"] == "GFLOP/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert abs(j["ms_per_step"] - j["spread"]["region_ms"][0] / 7) < 1e-3
+    for moved in ("secondary", "cpu_baseline", "kernel_us", "eager_ms_per_step", "no_prefetch", "dense_embedding_bag"):
+        assert j.get(moved) is None, moved
+    got = sorted(p.name for p in dump.iterdir())
+    assert got == ["core0.npy", "core1.npy", "core2.npy", "output.npy"], got
+    o = np.load(dump / "output.npy")
+    assert o.dtype == np.float32 and o.shape == (512, 64) and np.isfinite(o).all() and np.abs(o).max() > 0
+    cores = [np.load(dump / f"core{t}.npy") for t in range(3)]
+    assert [c.shape[-2] for c in cores] == [200, 220, 250] and all(np.isfinite(c).all() for c in cores)
 
 
 @pytest.mark.gpu

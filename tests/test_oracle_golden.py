@@ -9,7 +9,7 @@ import pytest
 
 import gen_inputs as G
 import oracle_lib as O
-from util import LR, EPS, adagrad_expected, assert_adagrad_close, assert_close, sgd_expected
+from util import LR, EPS, adagrad_expected, assert_adagrad_close, assert_close, load_golden, sgd_expected
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -59,7 +59,7 @@ def test_round4_cases(round4_cases):
 
 def big_case(tag):
     cfg, seed = {"cfg2": (G.CFG2, 1234), "cfg4": (G.CFG4, 4321), "r128": (G.R128, 2468)}[tag]
-    z = np.load(os.path.join(HERE, "golden", f"{tag}.npz"))
+    z = load_golden(os.path.join(HERE, "golden", f"{tag}.npz"))
     assert int(z["seed"][0]) == seed
     p, q, r = cfg["p"], cfg["q"], G.pad_ranks(cfg["ranks"], 3)
     E_, D = int(np.prod(p)), int(np.prod(q))
@@ -109,32 +109,45 @@ def test_hash_known_answers():
         assert O.hashtbl_find(int(k), keys) == want
 
 
-def test_hash_vs_reference_build():
-    """oracle/_ref/libhashref.so = the reference's own murmor_hash_3_32 compiled
-    from /root/reference/hashtbl_cuda_utils.cuh (oracle/Makefile)."""
-    import ctypes as C
-
-    so = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libhashref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref = C.CDLL(so)
-    ref.ref_hash64.restype = C.c_uint32
-    ref.ref_hash64.argtypes = [C.c_int64, C.c_int32]
-    ref.ref_hash32.restype = C.c_uint32
-    ref.ref_hash32.argtypes = [C.c_int32, C.c_int32]
+def hashref_cases():
+    """keys and table sizes of test_hash_vs_reference_build: (int64 keys, sizes, int32 keys, the int32 table size)"""
     rs = np.random.RandomState(3)
     keys = np.concatenate([rs.randint(-2 ** 62, 2 ** 62, size=4000), np.arange(-5, 200), [2 ** 63 - 1, -2 ** 63]])
-    for size in (1, 16, 1000, 1 << 20, 11_000_000, 2 ** 31 - 1):
-        for k in keys:
-            assert O.hash64(int(k), size) == ref.ref_hash64(int(k), size)
-    for k in rs.randint(-2 ** 31, 2 ** 31, size=2000):
-        assert O.hash32(int(k), 1000003) == ref.ref_hash32(int(k), 1000003)
+    keys32 = rs.randint(-2 ** 31, 2 ** 31, size=2000)
+    return keys, (1, 16, 1000, 1 << 20, 11_000_000, 2 ** 31 - 1), keys32, 1000003
+
+
+def test_hash_vs_reference_build():
+    """oracle/_ref/libhashref.so = the reference's own murmor_hash_3_32 compiled
+    from the reference's hashtbl_cuda_utils.cuh (oracle/Makefile); where that build is absent, what it returned for the same keys
+    (tests/golden/hashref_values.npz, tests/golden/make_hashref_values.py)."""
+    import ctypes as C
+
+    keys, sizes, keys32, size32 = hashref_cases()
+    so = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libhashref.so")
+    if os.path.exists(so):
+        ref = C.CDLL(so)
+        ref.ref_hash64.restype = C.c_uint32
+        ref.ref_hash64.argtypes = [C.c_int64, C.c_int32]
+        ref.ref_hash32.restype = C.c_uint32
+        ref.ref_hash32.argtypes = [C.c_int32, C.c_int32]
+        h64 = [[ref.ref_hash64(int(k), size) for k in keys] for size in sizes]
+        h32 = [ref.ref_hash32(int(k), size32) for k in keys32]
+    else:
+        z = np.load(os.path.join(HERE, "golden", "hashref_values.npz"))
+        assert (z["keys"] == keys).all() and z["sizes"].tolist() == list(sizes) and (z["keys32"] == keys32).all()
+        h64, h32 = z["hash64"].tolist(), z["hash32"].tolist()
+    for size, want in zip(sizes, h64):
+        for k, w in zip(keys, want):
+            assert O.hash64(int(k), size) == w
+    for k, w in zip(keys32, h32):
+        assert O.hash32(int(k), size32) == w
 
 
 def check_cfg5_tables(c, out, grads=None, sgd_cores=None):
     """a 26-table run at B = 512 (out [26, 512, 64], dense core gradients / SGD-updated cores [26, p_t, slice]) against
     the reference's results for the tables stored in tests/golden/cfg5.npz"""
-    z = np.load(os.path.join(HERE, "golden", "cfg5.npz"))
+    z = load_golden(os.path.join(HERE, "golden", "cfg5.npz"))
     assert int(z["seed"][0]) == G.CFG5_SEED and c["B"] == 512
     for k in z["tables"].tolist():
         assert_close(out[k], z[f"t{k}_out"], f"cfg5 table {k} out")

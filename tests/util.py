@@ -124,3 +124,63 @@ def rowwise_adagrad_segments_f64(grad, loc, rowidx, lr, eps, state, weight):
             w[idx] -= g[row] * (lr * (1.0 / (np.sqrt(old + g_avg_square) + eps)))
         i += sl
     return st, w
+
+
+# Golden vectors are committed in parts of at most GOLDEN_PART_BYTES each (<name>-<k>.npz, the arrays of <name> spread over them):
+# no committed file is larger than 1 MiB.  load_golden() reads them back as one {key: array} mapping.
+GOLDEN_PART_BYTES = 1000 * 1024
+
+
+class GoldenArrays(dict):
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden(path):
+    """tests/golden/<name>.npz -> {key: array}, from <name>.npz itself or from its parts <name>-1.npz, <name>-2.npz, ..."""
+    import glob
+    import os
+
+    stem = path[:-4] if path.endswith(".npz") else path
+    parts = [path] if os.path.exists(stem + ".npz") else sorted(glob.glob(glob.escape(stem) + "-*.npz"),
+                                                               key=lambda f: int(f[len(stem) + 1:-4]))
+    assert parts, f"no golden vectors at {stem}.npz or {stem}-<k>.npz"
+    out = GoldenArrays()
+    for f in parts:
+        with np.load(f) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
+def save_golden(path, blob):
+    """np.savez_compressed of `blob` as parts <name>-1.npz, <name>-2.npz, ... of at most GOLDEN_PART_BYTES each (arrays in
+    their insertion order; one part when it all fits); removes the files of an earlier save of <name>"""
+    import glob
+    import io
+    import os
+
+    stem = path[:-4] if path.endswith(".npz") else path
+    for f in [stem + ".npz"] + glob.glob(glob.escape(stem) + "-*.npz"):
+        if os.path.exists(f):
+            os.remove(f)
+
+    def packed(arrays):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **arrays)
+        return buf.getvalue()
+
+    parts, cur = [], {}
+    for k, v in blob.items():
+        trial = dict(cur, **{k: v})
+        if cur and len(packed(trial)) > GOLDEN_PART_BYTES:
+            parts.append(cur)
+            cur = {k: v}
+        else:
+            cur = trial
+    parts.append(cur)
+    for n, arrays in enumerate(parts, 1):
+        data = packed(arrays)
+        assert len(data) <= GOLDEN_PART_BYTES, f"{stem}: array(s) {list(arrays)} alone exceed {GOLDEN_PART_BYTES} bytes"
+        with open(f"{stem}-{n}.npz", "wb") as f:
+            f.write(data)
