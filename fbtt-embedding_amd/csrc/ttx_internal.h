@@ -173,6 +173,9 @@ int plan_build_batches(const Dims& d, int nbatch, long long nnz, const int* n_de
 
 long long* debug_stamps();  // debug stamp buffer (ttx_debug_stamps), or nullptr
 
+// dst[i] = i for i < n (ttx_pool.hip): the lookups' own positions as "bag rows" of ttx_tt_backward_rows
+int fill_iota64(int64_t* dst, long long n, hipStream_t stream);
+
 // --------------------------------------------------- duplicate lookups ----
 // Device-resident map of a batch onto its DISTINCT (table, index) pairs (include/ttx.h, ttx_dedup_build): the
 // contraction kernels then run once per distinct pair, bag pooling gathers a lookup's row through uid[], and the

@@ -2353,6 +2353,22 @@ int ttx_tt_rows(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indice
   return run_rows(d, nnz, P, tt_cores, rows, nullptr, 0, (hipStream_t)stream);
 }
 
+int ttx_tt_rows_p(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                  const float* const* tt_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                  ttx_stream_t stream) {
+  if (!plan) return ttx_tt_rows(g, D, nnz, indices, tableidx, tt_cores, rows, workspace, workspace_bytes, stream);
+  Dims d;
+  int rc = make_dims(g, &d);
+  if (rc) return rc;
+  if (nnz == 0) return TTX_OK;
+  rc = common_checks(d, D, nnz);
+  if (rc) return rc;
+  if (!tt_cores || !rows) TTX_FAIL(TTX_EINVAL, "NULL input");
+  if (((uintptr_t)rows) & 15) TTX_FAIL(TTX_EINVAL, "rows must be 16-byte aligned");
+  // (a four-core plan keeps the merged last cores of these lookups: ttx_tt_backward_rows on the same plan reuses them)
+  return run_rows(d, nnz, carve_plan(d, nnz, (void*)plan), tt_cores, rows, nullptr, 0, (hipStream_t)stream);
+}
+
 static int num_segments(const Dims& d, long long nnz, int MC, int t) {
   if (t == 1) return 0;  // (the pivot's hot slices are split by columns: hot_wgs)
   const long long total = (t == 1) ? (long long)max_chunks(d, nnz, MC) : nnz;
@@ -2414,6 +2430,31 @@ int ttx_tt_backward_w(const ttx_geom* g, int32_t optim, int32_t B, int32_t D, fl
                       const void* plan, void* workspace, size_t workspace_bytes, ttx_stream_t stream) {
   return tt_backward_impl(g, optim, B, D, lr, eps, nnz, indices, rowidx, tableidx, psw, d_output, tt_cores, optimizer_state,
                           d_tt_cores, plan, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+size_t ttx_tt_backward_rows_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz) {
+  const size_t b = ttx_tt_backward_workspace_bytes(g, 0, D, nnz);
+  return b ? b + align_up((size_t)nnz * sizeof(int64_t)) : 0;
+}
+
+int ttx_tt_backward_rows(const ttx_geom* g, int32_t optim, int32_t D, float lr, float eps, int64_t nnz,
+                         const int64_t* indices, const int64_t* tableidx, const float* d_rows,
+                         float* const* tt_cores, float* const* optimizer_state, float* const* d_tt_cores,
+                         const void* plan, void* workspace, size_t workspace_bytes, ttx_stream_t stream) {
+  // Every route addresses lookup n's gradient row as d_output + (tableidx[n] * B + row(n)) * D, row(n) = the plan's lrow or
+  // rowidx[n].  Here the table stride is 0 and the "bag rows" are the lookups' own positions (an iota at the front of the
+  // workspace; a plan built here carries them as lrow): the row read is d_rows + n * D on every route.
+  const size_t ib = nnz > 0 ? align_up((size_t)nnz * sizeof(int64_t)) : 0;
+  int64_t* pos = nullptr;
+  if (nnz > 0) {
+    if (!workspace || workspace_bytes < ib) TTX_FAIL(TTX_EWORKSPACE, "backward_rows workspace too small: %zu < %zu", workspace_bytes, ib);
+    pos = (int64_t*)workspace;
+    const int rc = fill_iota64(pos, nnz, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return tt_backward_impl(g, optim, /*B=*/0, D, lr, eps, nnz, indices, pos, tableidx, nullptr, d_rows, tt_cores, optimizer_state,
+                          d_tt_cores, plan, nnz > 0 ? (char*)workspace + ib : workspace, workspace_bytes - ib, stream, nullptr,
+                          nullptr);
 }
 
 int ttx_tt_backward_wc(const ttx_geom* g, int32_t optim, int32_t B, int32_t D, float lr, float eps,

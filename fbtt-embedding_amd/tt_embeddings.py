@@ -14,7 +14,8 @@ not on a GPU, the call raises.
 Extras beyond the reference's eleven names (used by tt_embeddings_ops.py and
 bench.py): `make_plan` (share the lookup plan between forward and backward; `dedup=True`: duplicate lookups of
 the batch share one contraction),
-`profile_*` (live kernel timings), `lib()` (the loaded ctypes library).
+`profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
+`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`.
 """
 import ctypes as C
 import os
@@ -154,6 +155,14 @@ def _load(path):
     L.ttx_tt_forward_dd.argtypes = [G, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.ttx_tt_backward_dd_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_backward_dd.argtypes = [G, i32, i32, i32, f32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # pooling modes (mean / max)
+    L.ttx_bag_mean_scale.argtypes = [i64, i32, vp, vp, vp, vp]
+    L.ttx_tt_rows_p.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_bag_max_pool.argtypes = [i64, i32, i64, vp, vp, vp, vp, vp]
+    L.ttx_bag_max_pool_backward.argtypes = [i64, i32, i64, vp, vp, vp, vp, vp]
+    L.ttx_tt_backward_rows_workspace_bytes.restype = C.c_size_t
+    L.ttx_tt_backward_rows_workspace_bytes.argtypes = [G, i32, i64]
+    L.ttx_tt_backward_rows.argtypes = [G, i32, i32, f32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     return L
 
 
@@ -742,6 +751,92 @@ def tt_rows(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx
                               None if tableidx is None else _i64(tableidx, "tableidx").data_ptr(), _ptr_array(cores),
                               rows.data_ptr(), ws.data_ptr(), ws.numel(), st))
     return rows
+
+
+# ---- pooling modes: nn.EmbeddingBag(mode="mean" / "max") (include/ttx.h "pooling modes") ----
+def bag_mean_scale(x: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """y[b, :] = x[b, :] / max(1, bag length) for x [..., D] holding nb = offsets.numel() - 1 rows (a new tensor)."""
+    dev = _dev(x)
+    x = _f32(x, "x")
+    offsets = _i64(offsets, "offsets")
+    nb, D = offsets.numel() - 1, x.size(-1)
+    if x.numel() != nb * D:
+        raise RuntimeError(f"tt_embeddings: bag_mean_scale needs {nb} rows of {D}, got {tuple(x.shape)}")
+    y = torch.empty_like(x)
+    with _guard(dev):
+        _check(lib().ttx_bag_mean_scale(nb, D, offsets.data_ptr(), x.data_ptr(), y.data_ptr(), _stream(dev)))
+    return y
+
+
+def tt_rows_p(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, tt_cores,
+              plan: Optional[Plan] = None) -> torch.Tensor:
+    """tt_rows with the batch's plan (make_plan(..., rowidx=None)): rows [nnz, D]; the plan then serves tt_backward_rows."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(tt_cores[0])
+    cores = _cores(tt_cores, g)
+    indices, tableidx = _i64(indices, "indices"), _i64(tableidx, "tableidx")
+    nnz = indices.numel()
+    rows = torch.empty((nnz, D), dtype=torch.float32, device=dev)
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, 0 if plan is not None else lb.ttx_plan_bytes(C.byref(g), nnz) + 256)
+    with _guard(dev):
+        _check(lb.ttx_tt_rows_p(C.byref(g), D, nnz, indices.data_ptr(), tableidx.data_ptr(), _ptr_array(cores), rows.data_ptr(),
+                                _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
+    return rows
+
+
+def bag_max_pool(rows: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (output [nb, D]: column-wise max of each bag's rows, argmax [nb, D] int32: the position of the row that holds it --
+    the first one on a tie, -1 for an empty bag, whose output is 0)."""
+    dev = _dev(rows)
+    rows, offsets = _f32(rows, "rows"), _i64(offsets, "offsets")
+    nb, D = offsets.numel() - 1, rows.size(1)
+    out = torch.empty((nb, D), dtype=torch.float32, device=dev)
+    arg = torch.empty((nb, D), dtype=torch.int32, device=dev)
+    with _guard(dev):
+        _check(lib().ttx_bag_max_pool(nb, D, rows.size(0), offsets.data_ptr(), rows.data_ptr(), out.data_ptr(), arg.data_ptr(),
+                                      _stream(dev)))
+    return out, arg
+
+
+def bag_max_pool_backward(d_output: torch.Tensor, argmax: torch.Tensor, offsets: torch.Tensor, nnz: int) -> torch.Tensor:
+    """d_rows [nnz, D]: lookup n's row carries the gradient of the columns it won in its bag, zeros elsewhere."""
+    dev = _dev(d_output)
+    d_output, offsets = _f32(d_output, "d_output"), _i64(offsets, "offsets")
+    if argmax.dtype != torch.int32 or not argmax.is_contiguous():
+        raise RuntimeError("tt_embeddings: argmax must be contiguous int32")
+    nb, D = offsets.numel() - 1, argmax.size(-1)
+    if d_output.numel() != nb * D or argmax.numel() != nb * D:
+        raise RuntimeError(f"tt_embeddings: bag_max_pool_backward needs {nb} rows of {D}")
+    d_rows = torch.empty((nnz, D), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(lib().ttx_bag_max_pool_backward(nb, D, nnz, offsets.data_ptr(), argmax.data_ptr(), d_output.data_ptr(),
+                                               d_rows.data_ptr(), _stream(dev)))
+    return d_rows
+
+
+def tt_backward_rows(optim, D, lr, eps, p, q, ranks, nnz, indices, tableidx, d_rows, tt_cores, state=None,
+                     plan: Optional[Plan] = None) -> Optional[List[torch.Tensor]]:
+    """the backward with one gradient row per lookup (d_rows [nnz, D]); optim OPTIM_SGD / OPTIM_ADAGRAD update the cores (and
+    the Adagrad state) in place, OPTIM_DENSE returns the core gradients.  plan: the one tt_rows_p ran on, or None."""
+    g = _geom(tt_cores[0].size(0), p, q, ranks)
+    dev = _dev(d_rows)
+    cores = _cores(tt_cores, g)
+    d_rows = _f32(d_rows, "d_rows")
+    if d_rows.dim() != 2 or d_rows.size(0) != nnz or d_rows.size(1) != D:
+        raise RuntimeError(f"tt_embeddings: d_rows must be [nnz, D] = [{nnz}, {D}], got {tuple(d_rows.shape)}")
+    indices, tableidx = _i64(indices, "indices"), _i64(tableidx, "tableidx")
+    grads = [torch.empty_like(c) for c in cores] if optim == OPTIM_DENSE else None
+    sptr = _ptr_array(_cores(state, g, "optimizer_state")) if optim == OPTIM_ADAGRAD else None
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, lb.ttx_tt_backward_rows_workspace_bytes(C.byref(g), D, nnz))
+    with _guard(dev):
+        _check(lb.ttx_tt_backward_rows(C.byref(g), optim, D, lr, eps, nnz, indices.data_ptr(), tableidx.data_ptr(),
+                                       d_rows.data_ptr(), _ptr_array(cores), sptr, None if grads is None else _ptr_array(grads),
+                                       _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
+    return grads
 
 
 def profile_enable(mask: int) -> None:

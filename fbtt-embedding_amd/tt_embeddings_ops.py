@@ -24,6 +24,8 @@ Deliberate differences (each is a superset or a fix):
   * nn.EmbeddingBag call forms: ctor keyword `include_last_offset` (default True =
     the reference's form), int32 indices / offsets, forward keyword
     `per_sample_weights`;
+  * nn.EmbeddingBag pooling modes: ctor keyword `mode` ("sum" = the reference's, "mean", "max";
+    TTMeanPoolFunction / TTMaxLookupFunction below);
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -334,6 +336,74 @@ class TTLookupFunction(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- #
+# pooling modes other than sum (nn.EmbeddingBag mode="mean" / "max"; include/ttx.h "pooling modes")
+# --------------------------------------------------------------------------- #
+
+POOLING_MODES = ("sum", "mean", "max")
+
+
+class TTMeanPoolFunction(torch.autograd.Function):
+    """mode="mean" around whatever the sum lookup returned: forward divides each bag's sum by its length, backward hands each
+    lookup the same share of its bag's gradient (the sum route's backward / fused optimizer then runs on the scaled gradient).
+    Empty bags stay zero."""
+
+    @staticmethod
+    def forward(ctx, summed: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        ctx.save_for_backward(offsets)
+        return _engine.bag_mean_scale(summed.contiguous(), offsets)
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        (offsets,) = ctx.saved_tensors
+        return _engine.bag_mean_scale(d_output.contiguous(), offsets), None
+
+
+class TTMaxLookupFunction(torch.autograd.Function):
+    """mode="max": the lookup's rows [nnz, D] (contraction without pooling), then the column-wise max per bag with the winning
+    lookup recorded per column (the first one on a tie, as PyTorch).  Backward: the bag gradient goes, column by column, to the
+    winning lookup's row only (a gradient row per lookup), and the ordinary backward / fused optimizer runs on those rows.  The
+    lookup plan is built without bag rows, so that forward and backward share it (four cores: the merged last cores too)."""
+
+    @staticmethod
+    def forward(ctx, B: int, D: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
+                indices: torch.Tensor, offsets: torch.Tensor, optimizer: OptimType, learning_rate: float, eps: float,
+                sparse: bool, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
+        num_tables = tt_cores[0].size(0)
+        nnz = indices.numel()
+        no_cache = indices.new_empty(0)
+        _, rowidx, tableidx, _, _ = _engine.preprocess_indices_sync(indices, offsets, num_tables, True, no_cache,
+                                                                     no_cache.int())
+        plan = _engine.make_plan(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, nnz, indices, tableidx)  # (no bag rows)
+        rows = _engine.tt_rows_p(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, list(tt_cores), plan)
+        out, argmax = _engine.bag_max_pool(rows, offsets)
+        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
+        ctx.D, ctx.nnz, ctx.plan = D, nnz, plan
+        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
+        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        ctx.save_for_backward(indices, offsets, tableidx, argmax)
+        return out.view(num_tables, B, D)
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        indices, offsets, tableidx, argmax = ctx.saved_tensors
+        p, q, ranks = ctx.geometry
+        cores = list(ctx.tt_cores)
+        d_rows = _engine.bag_max_pool_backward(d_output.contiguous(), argmax, offsets, ctx.nnz)
+        head: List[Optional[torch.Tensor]] = [None] * 12
+        if ctx.sparse:
+            if ctx.optimizer in _SGD_LIKE:
+                _engine.tt_backward_rows(_engine.OPTIM_SGD, ctx.D, ctx.learning_rate, 0.0, p, q, ranks, ctx.nnz, indices,
+                                         tableidx, d_rows, cores, None, ctx.plan)
+            else:
+                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, ctx.D, ctx.learning_rate, ctx.eps, p, q, ranks, ctx.nnz, indices,
+                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
+            return tuple(head + [None] * len(cores))
+        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, ctx.D, 0.0, 0.0, p, q, ranks, ctx.nnz, indices, tableidx, d_rows,
+                                         cores, None, ctx.plan)
+        return tuple(head + list(grads))
+
+
+# --------------------------------------------------------------------------- #
 # shape factoring (init-time helper; reference :359-418)
 # --------------------------------------------------------------------------- #
 
@@ -405,7 +475,7 @@ def suggested_tt_shapes(n: int, d: int = 3, allow_round_up: bool = True) -> List
 
 class TableBatchedTTEmbeddingBag(nn.Module):
     """`num_tables` TT-compressed embedding tables of identical shape looked up
-    in one pass (sum pooling, include_last_offset form: offsets has
+    in one pass (sum pooling -- or `mode="mean"` / `"max"` --, include_last_offset form: offsets has
     num_tables*B + 1 entries, bags ordered table-major)."""
 
     __constants__ = ["num_tables", "num_embeddings", "embedding_dim", "tt_shape", "tt_rank"]
@@ -416,8 +486,19 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  sparse: bool = True, use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
-                 reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None) -> None:
+                 reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
+                 mode: str = "sum") -> None:
         super().__init__()
+        # mode (trailing keyword, not in the reference): nn.EmbeddingBag's pooling -- "sum" (the reference's, the default here),
+        # "mean" (the bag sum over the bag length: a per-bag scale around the sum lookup, every route) or "max" (column-wise max,
+        # the gradient to the winning lookup only: rows, max pool and a per-lookup backward; no live cache, no dedup, no n_dev)
+        if mode not in POOLING_MODES:
+            raise ValueError(f"mode must be one of {POOLING_MODES}, got {mode!r}")
+        if mode == "max" and use_cache:
+            raise NotImplementedError("mode='max' does not support use_cache=True (the cache rows are pooled by sum)")
+        if mode == "max" and dedup:
+            raise NotImplementedError("mode='max' does not support dedup (duplicate lookups would share one winning row)")
+        self.mode = mode
         # deterministic_cache_update (trailing keyword, not in the reference): how the backward updates the CACHE rows.  True: the
         # cached lookups are grouped by cache row with a stable sort, a row's bag gradients added in index order, one writer per row --
         # cache_weight (and the row-wise Adagrad state) bit-identical from run to run (ttx_cache_backward_sorted).  False: the
@@ -671,7 +752,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         overlap does not apply: cache live, no C++ node, CPU tensors, empty batch, duplicate sharing."""
         fast = _native_node()
         if (fast is None or not self.warmup or not indices.is_cuda or indices.numel() == 0 or self._dedup_may_share(indices.numel())
-                or indices.dim() != 1 or offsets.dim() != 1 or self.__dict__.get("_split0", 0) > 1):
+                or indices.dim() != 1 or offsets.dim() != 1 or self.__dict__.get("_split0", 0) > 1
+                or self.__dict__.get("mode", "sum") == "max"):
             return False
         key = (id(indices), id(offsets))  # (identity: the entry keeps both objects alive, so neither id nor memory is reused)
         idx, off = self._normalise(indices, offsets)
@@ -709,7 +791,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         fast = _native_node()
         batches = list(batches)
         live = not self.warmup
-        if fast is None or not batches or self.__dict__.get("_split0", 0) > 1 or self._dedup_may_share(batches[0][0].numel()) or (live and not (self.use_cache and self.num_tables == 1)):
+        if (fast is None or not batches or self.__dict__.get("_split0", 0) > 1 or self._dedup_may_share(batches[0][0].numel())
+                or (live and not (self.use_cache and self.num_tables == 1)) or self.__dict__.get("mode", "sum") == "max"):
             return False
         norm, keys = [], []
         for indices, offsets in batches:
@@ -888,7 +971,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 raise RuntimeError("TableBatchedTTEmbeddingBag.forward(n_dev=): with a cache, part lookups (q0 > 4) or shared duplicates "
                                    "the live count is read back to the host -- not capturable in a hipGraph on this route")
             n = int(n_dev.item())
-            return self.forward(indices[:n].contiguous(), offsets)
+            return self._forward_sum(indices[:n].contiguous(), offsets)
         indices = indices.long() if indices.dtype != torch.int64 else indices
         offsets = offsets.long() if offsets.dtype != torch.int64 else offsets
         indices = indices if indices.is_contiguous() else indices.contiguous()
@@ -931,7 +1014,39 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         `n_dev` (round 5; not in the reference): one int32 on the device, the number of LIVE lookups -- `indices` then holds an
         upper bound (a fixed-capacity buffer), `offsets` (with its closing entry) describes exactly the first n_dev of them, and
         only those are planned, contracted, pooled and trained: no host read-back of the count (ttx_lookup_prologue_n).  What
-        the table-sharded module's ragged route hands its local lookup."""
+        the table-sharded module's ragged route hands its local lookup.
+        The bags are pooled by the constructor's `mode` ("sum": the reference's)."""
+        if self.__dict__.get("mode", "sum") != "sum":
+            return self._forward_mode(indices, offsets, warmup, per_sample_weights, n_dev)
+        return self._forward_sum(indices, offsets, warmup, per_sample_weights, n_dev)
+
+    def _forward_mode(self, indices, offsets, warmup, per_sample_weights, n_dev) -> torch.Tensor:
+        """mode="mean": the sum lookup (any route) scaled per bag; mode="max": TTMaxLookupFunction on the unsplit geometry."""
+        if per_sample_weights is not None:
+            raise ValueError(f"per_sample_weights is only supported with mode='sum' (as in torch), not mode={self.mode!r}")
+        if self.mode == "max":
+            if n_dev is not None:
+                raise NotImplementedError("mode='max' does not support forward(n_dev=)")
+            if indices.dim() != 1 or offsets.dim() != 1:
+                raise ValueError("indices and offsets must be 1-D (the 2-D fixed-length form of nn.EmbeddingBag is not supported)")
+            indices, offsets = self._normalise(indices, offsets)
+            if (offsets.numel() - 1) % self.num_tables != 0:
+                raise ValueError(f"offsets must describe num_tables * B bags, got {offsets.numel() - 1} bags for "
+                                 f"{self.num_tables} tables")
+            # (q0 > 4: the unsplit geometry on the generic kernels -- the part lookups of the sum route would split a bag's
+            #  columns over k part bags, each with its own winner per column, which is the same max, but their gradient rows
+            #  would need the part layout: not worth a route of its own)
+            return TTMaxLookupFunction.apply(
+                (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks,
+                indices.contiguous(), offsets.contiguous(), self.optimizer, self.learning_rate, self.eps, self.sparse,
+                list(self.optimizer_state), *self.tt_cores)
+        # mean: the bag lengths come from the offsets in their closing-entry form (n_dev: the caller's, which must have it)
+        bag_offsets = offsets.long() if n_dev is not None else self._normalise(indices, offsets)[1]
+        summed = self._forward_sum(indices, offsets, warmup, None, n_dev)
+        return TTMeanPoolFunction.apply(summed, bag_offsets.contiguous())
+
+    def _forward_sum(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
+                     per_sample_weights: Optional[torch.Tensor] = None, n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
         if n_dev is not None:
             if per_sample_weights is not None:  # (round 6, advisor: the weights were silently dropped on this route)
                 raise NotImplementedError("forward(n_dev=) does not take per_sample_weights")
@@ -1096,11 +1211,12 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  sparse: bool = True, use_cache: bool = True, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
-                 reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None) -> None:
+                 reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
+                 mode: str = "sum") -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
                          enforce_embedding_dim, device, include_last_offset, dedup, reference_exact_populate,
-                         deterministic_cache_update)
+                         deterministic_cache_update, mode)
 
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -216,6 +216,42 @@ int ttx_tt_backward_wc(const ttx_geom* g, int32_t optim, int32_t B, int32_t D, f
                        const int32_t* skip_dev, const int32_t* cache_loc, const float* cache_grad, float cache_scale,
                        float* cache_dst, int32_t* tail_done);
 
+/* ------------------------------ pooling modes: mean and max (not in the reference) -----
+ * nn.EmbeddingBag(mode="mean" / "max") over the same contraction (the reference pools by sum only).  Bags are described
+ * by offsets [nb + 1] int64 (closing entry included, table-major over the tables as everywhere): bag b covers positions
+ * [offsets[b], offsets[b + 1]) of the batch.  No atomics, one writer per element: bit-identical from run to run, nothing
+ * read back (capturable).  Float arrays 16-byte aligned with D % 4 == 0 take the float4 kernels, anything else the scalar ones.
+ *
+ *   ttx_bag_mean_scale         y[b, :] = x[b, :] / max(1, offsets[b + 1] - offsets[b]), x / y [nb, D] (y may be x): the mean
+ *                              from the bag sum of ttx_tt_forward*, and the share of a bag's gradient each lookup receives
+ *                              (scale d_output, then any sum-mode backward).  An empty bag stays 0.
+ *   ttx_tt_rows_p              ttx_tt_rows with a prebuilt plan (NULL = ttx_tt_rows): rows [nnz, D] (16-byte aligned) of a
+ *                              plan from ttx_plan_build with rowidx == NULL.  No workspace when a plan is given.  A four-core
+ *                              plan keeps the merged last cores of the call for ttx_tt_backward_rows on the same plan.
+ *   ttx_bag_max_pool           output [nb, D] = column-wise max over the bag's rows [nnz, D], argmax [nb, D] int32 = the
+ *                              position n (row of `rows`) that holds it: the lowest one on a tie (PyTorch's order: a strict >
+ *                              scanning the bag in index order).  Empty bag: 0 and -1.  One wave per bag.
+ *   ttx_bag_max_pool_backward  d_rows [nnz, D] = argmax[bag(n), e] == n ? d_output[bag(n), e] : 0 -- every element written
+ *                              once (lookups outside every bag: 0); no memset needed in front.
+ *   ttx_tt_backward_rows       ttx_tt_backward with ONE gradient row PER LOOKUP: lookup n's gradient is d_rows[n, :]
+ *                              ([nnz, D]) instead of d_output[tableidx[n], rowidx[n], :].  Same optimizers, same outputs.
+ *                              plan: NULL (built in the workspace), or the plan of ttx_tt_rows_p -- built WITHOUT bag rows
+ *                              (ttx_plan_build rowidx == NULL; a plan that carries bag rows addresses the wrong rows).
+ *                              Workspace: ttx_tt_backward_rows_workspace_bytes (the backward's plus nnz int64). */
+int ttx_bag_mean_scale(int64_t nb, int32_t D, const int64_t* offsets, const float* x, float* y, ttx_stream_t stream);
+int ttx_tt_rows_p(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                  const float* const* tt_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                  ttx_stream_t stream);
+int ttx_bag_max_pool(int64_t nb, int32_t D, int64_t nnz, const int64_t* offsets, const float* rows, float* output,
+                     int32_t* argmax, ttx_stream_t stream);
+int ttx_bag_max_pool_backward(int64_t nb, int32_t D, int64_t nnz, const int64_t* offsets, const int32_t* argmax,
+                              const float* d_output, float* d_rows, ttx_stream_t stream);
+size_t ttx_tt_backward_rows_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz);
+int ttx_tt_backward_rows(const ttx_geom* g, int32_t optim, int32_t D, float learning_rate, float eps, int64_t nnz,
+                         const int64_t* indices, const int64_t* tableidx, const float* d_rows,
+                         float* const* tt_cores, float* const* optimizer_state, float* const* d_tt_cores,
+                         const void* plan, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
+
 /* ----------------------------------------------- duplicate lookups -----
  * Not in the reference (which contracts every lookup on its own): a batch's lookups are mapped onto their
  * DISTINCT (table, index) pairs, the contraction runs once per pair, bag pooling gathers each lookup's row
