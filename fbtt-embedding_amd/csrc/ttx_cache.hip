@@ -323,22 +323,28 @@ __global__ __launch_bounds__(kCT) void cache_rows_gather_kernel(int N, int D, co
   for (int e = l; e < D; e += 32) dst[e] = src[e];
 }
 
-// scaled[n] = psw[n] * grad[rowidx[n]] and iota[n] = n for the cached entries: the cache backward kernels then take
-// (scaled, iota) in place of (grad_output, rowidx) -- every lookup brings its own weighted gradient row
+// scaled[n] = psw[n] * grad[rowidx[n]] for the cached entries (n >= the split point) and iota[n] = n for EVERY n: the cache backward
+// kernels then take (scaled, iota) in place of (grad_output, rowidx) -- every lookup brings its own weighted gradient row.  In front
+// of the split point scaled[n] = 0: no consumer reads it there (ttx.h, ttx_cache_backward_sorted), but the sorted update walks
+// EVERY position of the batch, and what it is handed is defined memory
 __global__ __launch_bounds__(kCT) void cache_scale_grad_kernel(int N, int D, const int* __restrict__ skip_dev,
                                                               const float* __restrict__ grad,
                                                               const int64_t* __restrict__ rowidx,
                                                               const float* __restrict__ psw,
                                                               float* __restrict__ scaled, int64_t* __restrict__ iota) {
   const int k = skip_dev ? max(0, min(N, *skip_dev)) : 0;
-  const int n = k + blockIdx.x * (kCT / 32) + threadIdx.x / 32;
+  const int n = blockIdx.x * (kCT / 32) + threadIdx.x / 32;
   const int l = threadIdx.x & 31;
   if (n >= N) return;
+  float* dst = scaled + (size_t)n * D;
+  if (l == 0) iota[n] = n;
+  if (n < k) {  // not a cached lookup: neither its bag row nor its weight is looked at
+    for (int e = l; e < D; e += 32) dst[e] = 0.f;
+    return;
+  }
   const float* g = grad + (size_t)rowidx[n] * D;
   const float wn = psw[n];
-  float* dst = scaled + (size_t)n * D;
   for (int e = l; e < D; e += 32) dst[e] = wn * g[e];
-  if (l == 0) iota[n] = n;
 }
 
 // The same sums for D % 4 == 0, wave64-native (the 32-lane-group kernel above keeps 1 group in 20 busy at 20 lookups
@@ -1208,25 +1214,30 @@ __device__ __forceinline__ float cs_seg_scan(float v, bool head, float* wsum, in
   return x;
 }
 
-__device__ __forceinline__ float cs_position_value(const DedupMap& M, int N, int i, const int64_t* __restrict__ rowidx,
-                                                   const float* __restrict__ g2, bool* head, int* n_out) {
+// (a lookup without a cache row -- in front of the split point, or loc outside [0, cache_size): the last run, key cache_size --
+//  counts 0 and its rowidx is NOT read: the caller owes nothing in front of the split point, ttx.h)
+__device__ __forceinline__ float cs_position_value(const DedupMap& M, int N, int i, long long cache_size,
+                                                   const int64_t* __restrict__ rowidx, const float* __restrict__ g2, bool* head,
+                                                   int* n_out) {
   *head = false;
   *n_out = -1;
   if (i >= N) return 0.f;
   const int n = M.occ[i];
   *n_out = n;
-  *head = i == 0 || M.uid[M.occ[i - 1]] != M.uid[n];
+  const int u = M.uid[n];
+  *head = i == 0 || M.uid[M.occ[i - 1]] != u;
+  if (M.uidx[u] >= cache_size) return 0.f;
   return g2[rowidx[n]];
 }
 
-__global__ __launch_bounds__(kCsBlock) void cs_scan_tails_kernel(DedupMap M, int N, const int64_t* __restrict__ rowidx,
-                                                                const float* __restrict__ g2, float* __restrict__ blk_tail,
+__global__ __launch_bounds__(kCsBlock) void cs_scan_tails_kernel(DedupMap M, int N, long long cache_size,
+                                                                const int64_t* __restrict__ rowidx, const float* __restrict__ g2, float* __restrict__ blk_tail,
                                                                 int* __restrict__ blk_head) {
   __shared__ float wsum[kCsBlock / kWave];
   __shared__ int whead[kCsBlock / kWave];
   bool head, nhb;
   int n;
-  const float v = cs_position_value(M, N, blockIdx.x * kCsBlock + threadIdx.x, rowidx, g2, &head, &n);
+  const float v = cs_position_value(M, N, blockIdx.x * kCsBlock + threadIdx.x, cache_size, rowidx, g2, &head, &n);
   float tail;
   int hh;
   cs_seg_scan(v, head, wsum, whead, &tail, &hh, &nhb);
@@ -1269,7 +1280,7 @@ __global__ __launch_bounds__(kCsBlock) void cs_scan_emit_kernel(DedupMap M, int 
   const int i = blockIdx.x * kCsBlock + threadIdx.x;
   bool head, nhb;
   int n;
-  const float v = cs_position_value(M, N, i, rowidx, g2, &head, &n);
+  const float v = cs_position_value(M, N, i, cache_size, rowidx, g2, &head, &n);
   float tail;
   int hh;
   float incl = cs_seg_scan(v, head, wsum, whead, &tail, &hh, &nhb);
@@ -1660,7 +1671,7 @@ int ttx_cache_backward_sorted(int32_t optim, int64_t nnz, const int32_t* skip_de
     float* mult = (float*)((char*)blk_carry + align_up((size_t)nblk * 4));
     hipLaunchKernelGGL(cs_bag_g2_kernel, dim3((unsigned)((num_bags + kCT / kWave - 1) / (kCT / kWave))), dim3(kCT), 0, st, (int)num_bags,
                        D, grad, g2);
-    hipLaunchKernelGGL(cs_scan_tails_kernel, dim3(nblk), dim3(kCsBlock), 0, st, M, N, rowidx, g2, blk_tail, blk_head);
+    hipLaunchKernelGGL(cs_scan_tails_kernel, dim3(nblk), dim3(kCsBlock), 0, st, M, N, (long long)cache_size, rowidx, g2, blk_tail, blk_head);
     hipLaunchKernelGGL(cs_scan_carry_kernel, dim3(1), dim3(1024), 0, st, nblk, blk_tail, blk_head, blk_carry);
     hipLaunchKernelGGL(cs_scan_emit_kernel, dim3(nblk), dim3(kCsBlock), 0, st, M, N, (long long)cache_size, rowidx, g2, blk_carry, lr, eps,
                        cache_optimizer_state, mult);
@@ -1669,7 +1680,8 @@ int ttx_cache_backward_sorted(int32_t optim, int64_t nnz, const int32_t* skip_de
     TTX_HIP(hipGetLastError());
     psw = mult;
   }
-  rc = gsum_launch(M, nnz, 0, D, rowidx, nullptr, psw, grad, Gu, gscr, st);
+  // (the run with the key cache_size -- the lookups without a cache row -- is not summed: neither rowidx nor grad is read for it)
+  rc = gsum_launch(M, nnz, 0, D, rowidx, nullptr, psw, grad, Gu, gscr, st, (long long)cache_size);
   if (rc) return rc;
   const float scale = optim == TTX_OPTIM_SGD ? -lr : -1.0f;
   const unsigned groups = (unsigned)((N + kCT / 16 - 1) / (kCT / 16));  // (nu <= N lives on the device: sized by N, surplus groups leave)

@@ -599,6 +599,8 @@ struct TTCachedLookupOp : public torch::autograd::Function<TTCachedLookupOp> {
     const float* gcache = go.data_ptr<float>();  // (weighted: every cached lookup's own scaled gradient row)
     Tensor scaled, iota;
     if (ppsw.defined()) {
+      // (ttx_cache_weighted_grad_n writes BOTH whole: iota[n] = n for every n, scaled = 0 in front of the split point -- the sorted
+      //  update below walks every position of the batch, and although it reads neither there, it is handed defined memory)
       scaled = at::empty({nnz, D}, go.options());
       iota = at::empty({nnz}, go.options().dtype(at::kLong));
       check(ttx_cache_weighted_grad_n(nnz, n_tt, (int32_t)D, go.data_ptr<float>(), rows, ppsw.data_ptr<float>(),

@@ -508,11 +508,13 @@ constexpr int kGsThreads = 256;
 __device__ __forceinline__ long long shfl64(long long v, int j) {
   return ((long long)__shfl((int)(v >> 32), j, 16) << 32) | (unsigned)__shfl((int)v, j, 16);
 }
-template <typename V>
+// kSkip (the sorted cache-row update, ttx_cache.hip): an occurrence whose key M.uidx[pair] >= skip_key has no cache row; its rowidx,
+// psw and gradient row are NOT read (what the caller holds there need not be valid), it adds 0 to a run nobody applies.
+template <typename V, bool kSkip>
 __global__ __launch_bounds__(kGsThreads) void gsum_slice_kernel(DedupMap M, int N, int B, int DV, const int64_t* __restrict__ rowidx,
                                                                const int64_t* __restrict__ tableidx,
                                                                const float* __restrict__ psw, const V* __restrict__ dout,
-                                                               V* __restrict__ Gu, V* __restrict__ P) {
+                                                               V* __restrict__ Gu, V* __restrict__ P, long long skip_key) {
   const int l = threadIdx.x & 15;
   const int s = blockIdx.x * (kGsThreads / 16) + threadIdx.x / 16;
   const int k0 = s * kGsSlice;
@@ -532,8 +534,9 @@ __global__ __launch_bounds__(kGsThreads) void gsum_slice_kernel(DedupMap M, int 
   for (int r = 0; r < kGsRounds; ++r) {
     off[r] = 0, w[r] = 1.f, up[r] = -1;
     if (n[r] >= 0) {
-      off[r] = (tableidx ? (long long)tableidx[n[r]] * B : 0ll) + rowidx[n[r]];  // (64-bit: tables * B may exceed 2^31)
       up[r] = M.uid[n[r]];
+      if (kSkip && M.uidx[up[r]] >= skip_key) { off[r] = -1; w[r] = 0.f; continue; }
+      off[r] = (tableidx ? (long long)tableidx[n[r]] * B : 0ll) + rowidx[n[r]];  // (64-bit: tables * B may exceed 2^31)
       if (psw) w[r] = psw[n[r]];
     }
   }
@@ -563,7 +566,10 @@ __global__ __launch_bounds__(kGsThreads) void gsum_slice_kernel(DedupMap M, int 
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const long long oj = shfl64(off[r], j);
-        if (j < cnt && ev) v[j] = dout[(size_t)oj * DV + e];
+        if (j < cnt && ev) {
+          if (kSkip && oj < 0) vzero(v[j]);
+          else v[j] = dout[(size_t)oj * DV + e];
+        }
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
@@ -2776,22 +2782,27 @@ size_t gsum_scratch_bytes(int D, long long nnz) {
   const size_t slices = ((size_t)nnz + kGsSlice - 1) / kGsSlice;
   return align_up(slices * 2 * (size_t)D * sizeof(float));
 }
-int gsum_launch(const DedupMap& M, long long nnz, int B, int D, const int64_t* rowidx, const int64_t* tableidx, const float* psw,
-                const float* d_output, float* Gu, void* scratch, hipStream_t st) {
-  const int N = (int)nnz;
+template <bool kSkip>
+static int gsum_launch_t(const DedupMap& M, int N, int B, int D, const int64_t* rowidx, const int64_t* tableidx, const float* psw,
+                         const float* d_output, float* Gu, float* Pp, hipStream_t st, long long skip_key) {
   const int blocks = ((N + kGsSlice - 1) / kGsSlice + kGsThreads / 16 - 1) / (kGsThreads / 16);
-  float* Pp = (float*)scratch;
   if (D % 4 == 0 && ((((uintptr_t)d_output) | ((uintptr_t)Gu)) & 15) == 0) {
-    hipLaunchKernelGGL(gsum_slice_kernel<float4>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D / 4, rowidx, tableidx, psw,
-                       (const float4*)d_output, (float4*)Gu, (float4*)Pp);
+    hipLaunchKernelGGL((gsum_slice_kernel<float4, kSkip>), dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D / 4, rowidx, tableidx, psw,
+                       (const float4*)d_output, (float4*)Gu, (float4*)Pp, skip_key);
     hipLaunchKernelGGL(gsum_fold_kernel<float4>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, D / 4, (const float4*)Pp, (float4*)Gu);
   } else {
-    hipLaunchKernelGGL(gsum_slice_kernel<float>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D, rowidx, tableidx, psw, d_output,
-                       Gu, Pp);
+    hipLaunchKernelGGL((gsum_slice_kernel<float, kSkip>), dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D, rowidx, tableidx, psw, d_output,
+                       Gu, Pp, skip_key);
     hipLaunchKernelGGL(gsum_fold_kernel<float>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, D, (const float*)Pp, Gu);
   }
   TTX_HIP(hipGetLastError());
   return TTX_OK;
+}
+// skip_key >= 0 (the sorted cache-row update): the occurrences of the keys >= skip_key are not summed -- see gsum_slice_kernel
+int gsum_launch(const DedupMap& M, long long nnz, int B, int D, const int64_t* rowidx, const int64_t* tableidx, const float* psw,
+                const float* d_output, float* Gu, void* scratch, hipStream_t st, long long skip_key) {
+  if (skip_key >= 0) return gsum_launch_t<true>(M, (int)nnz, B, D, rowidx, tableidx, psw, d_output, Gu, (float*)scratch, st, skip_key);
+  return gsum_launch_t<false>(M, (int)nnz, B, D, rowidx, tableidx, psw, d_output, Gu, (float*)scratch, st, -1ll);
 }
 }  // namespace ttx
 extern "C" {

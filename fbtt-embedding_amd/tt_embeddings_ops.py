@@ -308,7 +308,13 @@ class TTLookupFunction(torch.autograd.Function):
         p, q, ranks = ctx.geometry
         n_tt, n_c = ctx.nnz_tt, ctx.nnz_cached
         extra = {"plan": ctx.plan} if ctx.plan is not None else {}
-        det = {"deterministic": ctx.det} if ctx.det is not None else {}
+        det_flag = ctx.det
+        auto = getattr(_engine, "_use_sorted", None)
+        if det_flag is None and n_c > 0 and auto is not None:
+            # "auto" looks at the BATCH (misses + hits), as the C++ node does (csrc/ttx_torch.cpp kSortedAutoNnz: its split point
+            # stays on the device): both routes switch at the same batch size.  The engine's own default would look at n_c alone.
+            det_flag = auto(None, n_tt + n_c, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
+        det = {"deterministic": det_flag} if det_flag is not None else {}
         cores = list(ctx.tt_cores)
         d_output = d_output.contiguous()
         head: List[Optional[torch.Tensor]] = [None] * 19

@@ -393,8 +393,10 @@ int ttx_cache_backward_rowwise_adagrad_approx_n(int64_t nnz, const int32_t* skip
  *    (per_sample_weights == NULL: ttx_cache_forward_n);
  *  - ttx_cache_rows_n: rows[n] = cache_weight[loc[n]] for the cached entries -- with the contraction's rows of the
  *    misses in front (ttx_tt_forward_wr) ttx_psw_backward then yields d per_sample_weights for the whole batch;
- *  - ttx_cache_weighted_grad_n: scaled[n] = per_sample_weights[n] * grad_output[rowidx[n]], iota[n] = n for the
- *    cached entries: ttx_cache_backward_*_n(.., grad_output = scaled, rowidx = iota, ..) is the weighted backward. */
+ *  - ttx_cache_weighted_grad_n: scaled[n] = per_sample_weights[n] * grad_output[rowidx[n]] for the cached entries
+ *    (n >= *skip_dev), scaled[n] = 0 in front of them (where neither rowidx nor the weight is read) and iota[n] = n for
+ *    EVERY n -- both outputs are written whole: ttx_cache_backward_*_n / ttx_cache_backward_sorted(.., grad_output =
+ *    scaled, rowidx = iota, num_bags = nnz, ..) is the weighted backward. */
 int ttx_preprocess_indices_async_w(int64_t nnz, const int64_t* colidx, int64_t num_bags_total, const int64_t* offsets,
                                    int32_t num_tables, int32_t warmup, int64_t hashtbl_size, const int64_t* hashtbl,
                                    const int32_t* cache_state, int64_t* rowidx, int64_t* tableidx,
@@ -552,7 +554,11 @@ int ttx_profile_read(int which, int64_t* launches, double* total_ms);
  * order of a sequential execution, where the reference's depends on which warp arrives first).  num_bags: rows of grad
  * (row-wise Adagrad).  Up to 32,768 lookups (D % 4 == 0, D <= 256) it is ONE launch -- every work-group owns the rows
  * row % G == g, finds and groups them in LDS -- and needs no workspace; beyond that a chain of ~16 launches (stable radix sort, run
- * heads, ordered sums, apply).  The atomic entry points above stay: one launch, faster below ~300k cached lookups (row-wise
+ * heads, ordered sums, apply).
+ * CONTRACT: what lies in front of the split point is not read.  For a lookup without a cache row -- n < *skip_dev, or
+ * cache_locations[n] outside [0, cache_size) -- neither rowidx[n] nor any row of grad_output is dereferenced, on either route;
+ * cache_locations[n] is read only for n >= *skip_dev.  The caller may leave rowidx[0, *skip_dev) unset.  rowidx[n] of a cached
+ * lookup must lie in [0, num_bags) (not checked).  The atomic entry points above stay: one launch, faster below ~300k cached lookups (row-wise
  * Adagrad: ~60k). */
 size_t ttx_cache_backward_sorted_workspace_bytes(int64_t nnz, int64_t num_bags, int32_t D);
 int ttx_cache_backward_sorted(int32_t optim, int64_t nnz, const int32_t* skip_dev, int64_t num_bags, int32_t D,

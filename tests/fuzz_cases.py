@@ -9,6 +9,7 @@ cache gather / SGD scatter.
 
 A fixed-seed slice of each runs under `-m gpu` (tests/test_fuzz_gpu.py); scripts/fuzz_plan.py and
 scripts/fuzz_cache.py run them for a time budget."""
+import ctypes as C
 import time
 
 import numpy as np
@@ -187,5 +188,37 @@ def run_cache_cases(seed=0, max_cases=None, budget=None):
             dw = t(w)
             E.cache_backward_sgd(nnz - ntt, t(grad), t(loc), t(rowidx), 0.1, dw)
             assert_close(dw.cpu().numpy(), w_ref, what + f" cache_backward_sgd D={D}", rtol=5e-5, atol_scale=1e-5)  # (float atomics in hardware order; measured worst: 0.2x the default bound)
+            # the weighted backward on the sorted entry over the WHOLE partitioned batch (ttx_cache_weighted_grad_n, then
+            # ttx_cache_backward_sorted behind the device-side split point): every cached lookup brings its own row weight x bag
+            # gradient.  The bag rows and weights in front of the split point are poisoned -- an extra, in-range gradient row of NaN,
+            # NaN weights --: nothing in front of the split point may be read (include/ttx.h).  (Draws from a stream of their own:
+            # the cases above stay what they were.)
+            rs2 = np.random.RandomState([seed, n, 77])
+            psw = (rs2.rand(nnz) * 2 - 0.5).astype(np.float32)
+            psw[rs2.rand(nnz) < 0.1] = 0.0
+            psw[:ntt] = np.nan
+            grad2 = np.concatenate([grad, np.full((1, D), np.nan, dtype=np.float32)])
+            row_all = np.concatenate([np.full(ntt, B, dtype=np.int64), rowidx])
+            loc_all = t(exp[4].astype(np.int32))
+            skip = torch.tensor([ntt], dtype=torch.int32, device=dev)
+            scaled = torch.full((nnz, D), float("nan"), device=dev)
+            iota = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+            dg2, dpsw, drow = t(grad2), t(psw), t(row_all)
+            L = E.lib()
+            assert L.ttx_cache_weighted_grad_n(C.c_int64(nnz), C.c_void_p(skip.data_ptr()), C.c_int32(D), C.c_void_p(dg2.data_ptr()),
+                                               C.c_void_p(drow.data_ptr()), C.c_void_p(dpsw.data_ptr()), C.c_void_p(scaled.data_ptr()),
+                                               C.c_void_p(iota.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+            assert torch.equal(iota, torch.arange(nnz, device=dev)), what + " iota must be written for every lookup"
+            assert bool(torch.isfinite(scaled[ntt:]).all()) and not bool(scaled[:ntt].any()), what + " scaled rows"
+            scaled[:ntt] = float("nan")  # (the sorted entry is owed nothing there either)
+            delta = np.zeros((cs, D))
+            np.add.at(delta, loc, psw[ntt:].astype(np.float64)[:, None] * grad[rowidx].astype(np.float64))
+            # (tests/test_cache_gpu.py::test_sorted_cache_update_edge_cases: a row that takes most of a batch of tens of thousands of
+            #  lookups is an fp32 sum of that many terms, here of mixed sign)
+            tol = dict(rtol=5e-5, atol_scale=1e-5) if nnz >= 30000 or cs == 1 else {}
+            for optim, target in ((E.OPTIM_SGD, t(w)), (E.OPTIM_DENSE, torch.full((cs, D), 7.0, device=dev))):
+                E._cache_backward_sorted(optim, nnz, scaled, loc_all, iota, 0.1, 0.0, None, target, skip_dev=skip)
+                assert_close(target.cpu().numpy(), w.astype(np.float64) - 0.1 * delta if optim == E.OPTIM_SGD else delta,
+                             what + f" weighted sorted cache update optim={optim} D={D}", **tol)
         n += 1
     return n

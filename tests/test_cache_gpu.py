@@ -337,15 +337,25 @@ def test_sorted_cache_update_is_deterministic_and_matches_the_oracle(n, D, cs, B
         assert_close(st_o, st64, "oracle rowwise adagrad state vs the float64 restatement of cu:1735-1795", **tol)
         assert_close(w_o, w64, "oracle rowwise adagrad weights vs the float64 restatement", **tol)
         assert_close(ada[0][1], w64, "sorted rowwise adagrad weights vs the float64 restatement", **tol)
-    # behind a device-side split point, with uncached entries (-1) in front of it
-    import ctypes as C
+    # behind a device-side split point, with uncached entries (-1) in front of it.  What lies in front of the split point is NOT
+    # READ (include/ttx.h): the prefix's rowidx points at an extra gradient row -- in range, so that a build that does read it stays
+    # in bounds -- filled with NaN, and its cache locations are either -1 or a real row (they are not looked at either); one NaN
+    # that travelled into a sum, a g2 or a scan would show in every row behind it.  All three optimizers, bit for bit.
     k = 777
-    loc2 = t(np.concatenate([np.full(k, -1, dtype=np.int32), loc]))
-    row2 = t(np.concatenate([np.zeros(k, dtype=np.int64), rowidx]))
+    grad2 = t(np.concatenate([grad, np.full((1, D), np.nan, dtype=np.float32)]))
+    loc2 = t(np.concatenate([np.where(np.arange(k) % 2 == 0, -1, loc[0]).astype(np.int32), loc]))
+    row2 = t(np.concatenate([np.full(k, B, dtype=np.int64), rowidx]))
     skip = torch.tensor([k], dtype=torch.int32, device=DEV)
     dw2 = t(w)
-    E._cache_backward_sorted(E.OPTIM_SGD, n + k, dg, loc2, row2, 0.1, 0.0, None, dw2, skip_dev=skip)
-    assert np.array_equal(dw2.cpu().numpy(), runs[0]), "the split point must not change a bit"
+    E._cache_backward_sorted(E.OPTIM_SGD, n + k, grad2, loc2, row2, 0.1, 0.0, None, dw2, skip_dev=skip)
+    assert np.array_equal(dw2.cpu().numpy(), runs[0]), "SGD: the split point must not change a bit"
+    gd2 = torch.full((cs, D), 7.0, device=DEV)
+    E._cache_backward_sorted(E.OPTIM_DENSE, n + k, grad2, loc2, row2, 0.0, 0.0, None, gd2, skip_dev=skip)
+    assert np.array_equal(gd2.cpu().numpy(), gd[0]), "dense: the split point must not change a bit"
+    dst2, dwa2 = t(st0), t(w)
+    E._cache_backward_sorted(E.OPTIM_ADAGRAD, n + k, grad2, loc2, row2, 0.1, 1e-4, dst2, dwa2, skip_dev=skip)
+    assert np.array_equal(dst2.cpu().numpy(), ada[0][0]) and np.array_equal(dwa2.cpu().numpy(), ada[0][1]), \
+        "row-wise Adagrad: the split point must not change a bit"
 
 
 @pytest.mark.parametrize("n,D,cs,what", [

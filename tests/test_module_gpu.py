@@ -1105,6 +1105,7 @@ def test_per_sample_weights_with_a_live_cache(node, optim, det):
     ref.backward(d_out)
     cores0 = [c.detach().clone() for c in a.tt_cores]
     cw0 = a.cache_weight.detach().clone()
+    cst0 = None if a.cache_optimizer_state is None else a.cache_optimizer_state.detach().clone()
     w = psw.clone().requires_grad_(True)
     out = a(idx, off, per_sample_weights=w)
     assert_close(out.detach().cpu().numpy(), ref.detach().cpu().numpy(), "weighted forward, cache live")
@@ -1126,6 +1127,23 @@ def test_per_sample_weights_with_a_live_cache(node, optim, det):
         assert torch.equal(moved, touched)
         step = a.cache_weight.detach() - cw0
         assert bool(((step * ref_cw.grad).sum(dim=1)[touched] < 0).all())
+        # ... and by how much: the float64 restatement of the reference's kernel over every cached lookup's own gradient row
+        # (weight x bag gradient), in the order the partition leaves the hits in -- behind the misses, reversed.  The state totals
+        # do not depend on the order (both routes); the rows' values are defined on the sorted route (index order within a row).
+        from util import rowwise_adagrad_segments_f64
+        pos = np.nonzero(hit.cpu().numpy())[0][::-1]
+        bag = np.searchsorted(off.cpu().numpy(), pos, side="right") - 1
+        rows64 = d_out.cpu().numpy().astype(np.float64)[bag] * psw.cpu().numpy().astype(np.float64)[pos][:, None]
+        row_of_key = np.full(E_, -1, dtype=np.int64)
+        row_of_key[ck.cpu().numpy()] = crow.cpu().numpy()
+        st64, w64 = rowwise_adagrad_segments_f64(rows64, row_of_key[idx.cpu().numpy()[pos]], np.arange(pos.size), 0.05, a.eps,
+                                                 cst0.cpu().numpy().reshape(-1)[:200], cw0.cpu().numpy())
+        # (the row-wise state is the first cache_size floats of the buffer, as in the reference)
+        assert_close(a.cache_optimizer_state.detach().cpu().numpy().reshape(-1)[:200], st64, "cache optimizer state totals",
+                     rtol=2e-5, atol_scale=4e-6)  # (tests/test_cache_gpu.py, row-wise Adagrad state: a running fp32 sum in another association)
+        if det:
+            assert_close(a.cache_weight.detach().cpu().numpy(), w64, "cache rows after row-wise Adagrad, sorted",
+                         rtol=2e-5, atol_scale=4e-6)
     # without a gradient for the weights, and an unweighted call afterwards, the module keeps working
     a(idx, off, per_sample_weights=psw).backward(d_out)
     a(idx, off).backward(d_out)
