@@ -15,7 +15,7 @@ Extras beyond the reference's eleven names (used by tt_embeddings_ops.py and
 bench.py): `make_plan` (share the lookup plan between forward and backward; `dedup=True`: duplicate lookups of
 the batch share one contraction),
 `profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
-`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`.
+`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, and padded bags' `bags_compact`.
 """
 import ctypes as C
 import os
@@ -163,6 +163,10 @@ def _load(path):
     L.ttx_tt_backward_rows_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_backward_rows_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_backward_rows.argtypes = [G, i32, i32, f32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    # padded bags (padding_idx)
+    L.ttx_bags_compact_workspace_bytes.restype = C.c_size_t
+    L.ttx_bags_compact_workspace_bytes.argtypes = [i64, i64]
+    L.ttx_bags_compact.argtypes = [i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
     return L
 
 
@@ -837,6 +841,38 @@ def tt_backward_rows(optim, D, lr, eps, p, q, ranks, nnz, indices, tableidx, d_r
                                        d_rows.data_ptr(), _ptr_array(cores), sptr, None if grads is None else _ptr_array(grads),
                                        _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
     return grads
+
+
+# ---- padded bags: nn.EmbeddingBag(padding_idx=) (include/ttx.h "padded bags") ----
+def bags_compact(indices: torch.Tensor, offsets: Optional[torch.Tensor], L: int, padding_idx: int
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Drop the slots that hold `padding_idx`, keeping the order of the others.  Bags: `offsets` [nb + 1] int64 with the closing
+    entry, or None for indices.numel() // L bags of L slots each.  -> (out_indices [nnz]: the live slots, then zeros;
+    out_offsets [nb + 1]: the bags of the live slots; n_live: one int32 on the device = out_offsets[nb]).  No host read-back."""
+    dev = _dev(indices)
+    indices = _i64(indices, "indices").reshape(-1)
+    nnz = indices.numel()
+    if offsets is not None:
+        offsets = _i64(offsets, "offsets")
+        nb = offsets.numel() - 1
+        if nb < 0:
+            raise RuntimeError("tt_embeddings: offsets must hold the closing entry")
+    else:
+        L = int(L)
+        if L < 0 or (L == 0 and nnz != 0) or (L > 0 and nnz % L != 0):
+            raise RuntimeError(f"tt_embeddings: bags_compact without offsets needs bags of L slots, got {nnz} slots for L = {L}")
+        nb = nnz // L if L > 0 else 0
+    out_i = torch.empty(nnz, dtype=torch.int64, device=dev)
+    out_o = torch.empty(nb + 1, dtype=torch.int64, device=dev)
+    n_live = torch.empty(1, dtype=torch.int32, device=dev)
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, lb.ttx_bags_compact_workspace_bytes(nb, nnz))
+    with _guard(dev):
+        _check(lb.ttx_bags_compact(nb, nnz, indices.data_ptr(), None if offsets is None else offsets.data_ptr(), int(L),
+                                   int(padding_idx), out_i.data_ptr(), out_o.data_ptr(), n_live.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), st))
+    return out_i, out_o, n_live
 
 
 def profile_enable(mask: int) -> None:

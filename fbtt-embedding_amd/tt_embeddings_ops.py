@@ -26,6 +26,8 @@ Deliberate differences (each is a superset or a fix):
     `per_sample_weights`;
   * nn.EmbeddingBag pooling modes: ctor keyword `mode` ("sum" = the reference's, "mean", "max";
     TTMeanPoolFunction / TTMaxLookupFunction below);
+  * nn.EmbeddingBag's padded batches: ctor keyword `padding_idx` and the 2-D fixed-length input `indices[N, L]` with
+    `offsets=None`; the padding is dropped on the device (`bags_compact`) in front of the lookup;
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -348,6 +350,19 @@ class TTLookupFunction(torch.autograd.Function):
 POOLING_MODES = ("sum", "mean", "max")
 
 
+def _normalise_padding_idx(padding_idx, num_embeddings: int) -> Optional[int]:
+    """torch.nn.EmbeddingBag's rule: None, or an int in [-num_embeddings, num_embeddings), negative values counted from the
+    end; stored normalised.  Anything else is a ValueError."""
+    if padding_idx is None:
+        return None
+    if isinstance(padding_idx, bool) or not isinstance(padding_idx, (int, np.integer)):
+        raise ValueError(f"padding_idx must be None or an int, got {padding_idx!r}")
+    padding_idx = int(padding_idx)
+    if not -num_embeddings <= padding_idx < num_embeddings:
+        raise ValueError(f"padding_idx must be within [-{num_embeddings}, {num_embeddings}), got {padding_idx}")
+    return padding_idx + num_embeddings if padding_idx < 0 else padding_idx
+
+
 class TTMeanPoolFunction(torch.autograd.Function):
     """mode="mean" around whatever the sum lookup returned: forward divides each bag's sum by its length, backward hands each
     lookup the same share of its bag's gradient (the sum route's backward / fused optimizer then runs on the scaled gradient).
@@ -493,7 +508,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
                  reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
-                 mode: str = "sum") -> None:
+                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
         super().__init__()
         # mode (trailing keyword, not in the reference): nn.EmbeddingBag's pooling -- "sum" (the reference's, the default here),
         # "mean" (the bag sum over the bag length: a per-bag scale around the sum lookup, every route) or "max" (column-wise max,
@@ -505,6 +520,12 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         if mode == "max" and dedup:
             raise NotImplementedError("mode='max' does not support dedup (duplicate lookups would share one winning row)")
         self.mode = mode
+        # padding_idx (trailing keyword, not in the reference): nn.EmbeddingBag's -- lookups of this index (the same value in every
+        # table) contribute nothing to their bag, receive no gradient and are not counted by the cache's frequency table; a bag of
+        # padding only is zero in every mode.  The slots are dropped on the device in front of the lookup (include/ttx.h "padded
+        # bags"), so they cost no contraction.  A TT table holds no independent zero row: full_weight()[padding_idx] is whatever
+        # the cores give, it is just never looked up through a padded call.
+        self.padding_idx = _normalise_padding_idx(padding_idx, int(num_embeddings))
         # deterministic_cache_update (trailing keyword, not in the reference): how the backward updates the CACHE rows.  True: the
         # cached lookups are grouped by cache row with a stable sort, a row's bag gradients added in index order, one writer per row --
         # cache_weight (and the row-wise Adagrad state) bit-identical from run to run (ttx_cache_backward_sorted).  False: the
@@ -740,13 +761,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)
 
     # -------------------------------------------------------------- prefetch
-    def _normalise(self, indices: torch.Tensor, offsets: torch.Tensor):
+    def _normalise(self, indices: torch.Tensor, offsets: torch.Tensor, closed: bool = False):
+        """closed: the offsets carry their closing entry whatever include_last_offset says (the ones this module built itself)"""
         indices, offsets = indices.long(), offsets.long()
-        if not self.include_last_offset:
+        if not self.include_last_offset and not closed:
             offsets = torch.cat([offsets, offsets.new_full((1,), indices.numel())])
         return indices, offsets
 
-    def prefetch(self, indices: torch.Tensor, offsets: torch.Tensor) -> bool:
+    def prefetch(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> bool:
         """Not in the reference.  Run the lookup prologue of a COMING batch now, on a side stream: hash-table frequency
         update, offsets -> bag rows and the lookup plan depend on the batch's indices only, not on the cores, so they
         can overlap the backward of the step before (call it once the next batch's tensors exist, before
@@ -755,7 +777,10 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         and events only; captures into a hipGraph as a forked branch.  (Host cost of a call: ~25 us of stream / event
         handling -- worth it inside a captured step or for steps beyond ~0.1 ms; an eager loop of small steps is better served
         by prefetch_many(), one launch for a round of batches.)  Returns False (and does nothing) whenever the
-        overlap does not apply: cache live, no C++ node, CPU tensors, empty batch, duplicate sharing."""
+        overlap does not apply: cache live, no C++ node, CPU tensors, empty batch, duplicate sharing, a module with padding_idx
+        or 2-D indices (a prologue planned ahead would be over the uncompacted slots)."""
+        if self.__dict__.get("padding_idx") is not None or offsets is None or indices.dim() != 1:
+            return False
         fast = _native_node()
         if (fast is None or not self.warmup or not indices.is_cuda or indices.numel() == 0 or self._dedup_may_share(indices.numel())
                 or indices.dim() != 1 or offsets.dim() != 1 or self.__dict__.get("_split0", 0) > 1
@@ -793,9 +818,12 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         frequency updates, cache lookups, hit / miss partitions and miss plans are done the same way
         (`ttx_lookup_prologue_cached_multi`, three launches); cache_populate() / reset_cache() drop what was planned.
         Returns False (and does nothing) where the prologue cannot be planned ahead: no C++ node, CPU tensors, empty
-        batches, batches of different sizes, duplicate sharing, a live cache over several tables."""
+        batches, batches of different sizes, duplicate sharing, a live cache over several tables, a module with padding_idx, 2-D
+        indices."""
         fast = _native_node()
         batches = list(batches)
+        if self.__dict__.get("padding_idx") is not None or any(o is None or i.dim() != 1 for i, o in batches):
+            return False
         live = not self.warmup
         if (fast is None or not batches or self.__dict__.get("_split0", 0) > 1 or self._dedup_may_share(batches[0][0].numel())
                 or (live and not (self.use_cache and self.num_tables == 1)) or self.__dict__.get("mode", "sum") == "max"):
@@ -843,6 +871,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         self.__dict__.pop("_fa", None)
         self.__dict__.pop("_fc", None)
         self.__dict__.pop("_sh0", None)  # (the padded copy of core 0 belongs to the old tensors' device / dtype)
+        self.__dict__.pop("_fixed_off", None)
         return super()._apply(fn, *a, **kw)
 
     def _evict_oldest_prefetched(self) -> None:
@@ -870,7 +899,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         """copy.deepcopy / torch.save of the module: the prefetch side stream and the planned-ahead batches (device
         buffers, HIP events) belong to this process and this point in time -- they are recreated at first use."""
         state = self.__dict__.copy()
-        for k in ("_pf_stream", "_prefetched", "_pf_key", "_pf_counted", "_pf_evicted", "_fa", "_fc"):
+        for k in ("_pf_stream", "_prefetched", "_pf_key", "_pf_counted", "_pf_evicted", "_fa", "_fc", "_fixed_off"):
             state.pop(k, None)
         return state
 
@@ -977,7 +1006,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 raise RuntimeError("TableBatchedTTEmbeddingBag.forward(n_dev=): with a cache, part lookups (q0 > 4) or shared duplicates "
                                    "the live count is read back to the host -- not capturable in a hipGraph on this route")
             n = int(n_dev.item())
-            return self._forward_sum(indices[:n].contiguous(), offsets)
+            return self._forward_sum(indices[:n].contiguous(), offsets, closed=True)  # (n_dev: offsets with their closing entry)
         indices = indices.long() if indices.dtype != torch.int64 else indices
         offsets = offsets.long() if offsets.dtype != torch.int64 else offsets
         indices = indices if indices.is_contiguous() else indices.contiguous()
@@ -1012,7 +1041,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         st[1] -= 1
         return st[0], False
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None, n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> [num_tables, B, D].  (`warmup` is ignored like in the reference,
         which uses self.warmup, :822,:841.)  int32 indices / offsets are accepted; with
@@ -1021,12 +1050,98 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         upper bound (a fixed-capacity buffer), `offsets` (with its closing entry) describes exactly the first n_dev of them, and
         only those are planned, contracted, pooled and trained: no host read-back of the count (ttx_lookup_prologue_n).  What
         the table-sharded module's ragged route hands its local lookup.
-        The bags are pooled by the constructor's `mode` ("sum": the reference's)."""
-        if self.__dict__.get("mode", "sum") != "sum":
+        The bags are pooled by the constructor's `mode` ("sum": the reference's).
+        nn.EmbeddingBag's padded batches: `indices` [N, L] with `offsets=None` is N = num_tables * B bags of L slots each
+        (table-major, `per_sample_weights` then [N, L] too), and with the constructor's `padding_idx` the slots that hold it are
+        dropped in front of the lookup (`_forward_padded`)."""
+        d = self.__dict__
+        if offsets is None or indices.dim() != 1 or d.get("padding_idx") is not None:
+            return self._forward_padded(indices, offsets, warmup, per_sample_weights, n_dev)
+        if d.get("mode", "sum") != "sum":
             return self._forward_mode(indices, offsets, warmup, per_sample_weights, n_dev)
         return self._forward_sum(indices, offsets, warmup, per_sample_weights, n_dev)
 
-    def _forward_mode(self, indices, offsets, warmup, per_sample_weights, n_dev) -> torch.Tensor:
+    def _fixed_offsets(self, device: torch.device, N: int, L: int) -> torch.Tensor:
+        """arange(0, N L + 1, L): the offsets (closing entry included) of N bags of L slots, kept per (device, N, L)"""
+        cache = self.__dict__.setdefault("_fixed_off", {})
+        key = (device, N, L)
+        off = cache.get(key)
+        if off is None:
+            while len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            off = torch.arange(0, N * L + 1, L, dtype=torch.int64, device=device) if L > 0 \
+                else torch.zeros(N + 1, dtype=torch.int64, device=device)
+            cache[key] = off
+        return off
+
+    def _forward_closed(self, indices, offsets, warmup, per_sample_weights) -> torch.Tensor:
+        """the existing routes on offsets that carry their closing entry"""
+        if self.__dict__.get("mode", "sum") != "sum":
+            return self._forward_mode(indices, offsets, warmup, per_sample_weights, None, closed=True)
+        return self._forward_sum(indices, offsets, warmup, per_sample_weights, None, closed=True)
+
+    def _forward_padded(self, indices, offsets, warmup, per_sample_weights, n_dev) -> torch.Tensor:
+        """nn.EmbeddingBag's 2-D fixed-length input and padding_idx.  Without padding_idx the 2-D input is
+        the flattened batch with offsets 0, L, 2L, ...; with it the padding slots are dropped in front of the lookup: on the
+        device by `bags_compact` + the n_dev route (sum / mean: no host read-back, capturable where forward(n_dev=) is), with a
+        read-back of the live count for max (forward(n_dev=) is not offered there), with torch ops where per_sample_weights must
+        keep their autograd path or the tensors are on the CPU."""
+        pad = self.__dict__.get("padding_idx")
+        mode = self.__dict__.get("mode", "sum")
+        if n_dev is not None:
+            raise NotImplementedError("forward(n_dev=) takes a compacted 1-D batch: not 2-D indices, not a module with padding_idx")
+        if indices.dim() == 2:
+            if offsets is not None:
+                raise ValueError("if indices is 2-D, offsets has to be None: indices is a batch of fixed-length bags (as in torch)")
+            N, L = int(indices.size(0)), int(indices.size(1))
+        elif indices.dim() == 1:
+            if offsets is None:
+                raise ValueError("offsets has to be a 1-D tensor when indices is 1-D (as in torch)")
+            if offsets.dim() != 1:
+                raise ValueError("offsets must be 1-D")
+            L = 0
+        else:
+            raise ValueError(f"indices must be 1-D or 2-D, got {indices.dim()}-D")
+        if per_sample_weights is not None:
+            if mode != "sum":
+                raise ValueError(f"per_sample_weights is only supported with mode='sum' (as in torch), not mode={mode!r}")
+            if per_sample_weights.shape != indices.shape:
+                raise ValueError("per_sample_weights must have the shape of indices")
+            per_sample_weights = per_sample_weights.reshape(-1)
+        if offsets is None:  # N bags of L slots; with padding on the device the kernel takes L itself
+            indices = indices.reshape(-1)
+            if pad is None or L == 0 or per_sample_weights is not None or not indices.is_cuda:
+                offsets = self._fixed_offsets(indices.device, N, L)
+        else:
+            indices, offsets = self._normalise(indices, offsets)
+            N = offsets.numel() - 1
+        if N % self.num_tables != 0:
+            raise ValueError(f"the batch must hold num_tables * B bags, got {N} bags for {self.num_tables} tables")
+        if pad is None:
+            return self._forward_closed(indices, offsets, warmup, per_sample_weights)
+        if per_sample_weights is not None or not indices.is_cuda:
+            # torch ops: boolean indexing keeps the weights' autograd path (padding slots get a zero weight gradient) -- and is what
+            # the tests' CPU engine runs.  The number of live slots shapes the result: a host synchronisation.
+            if indices.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("padding_idx with per_sample_weights drops the padding with torch ops, whose output shape is the "
+                                   "live count read back to the host -- not capturable in a hipGraph")
+            keep = indices != pad
+            before = torch.cat([torch.zeros(1, dtype=torch.int64, device=indices.device), torch.cumsum(keep, 0)])
+            offsets = before[offsets.long().clamp(0, indices.numel())]  # live slots in front of every bag start
+            if per_sample_weights is not None:
+                per_sample_weights = per_sample_weights[keep]
+            return self._forward_closed(indices[keep], offsets, warmup, per_sample_weights)
+        if mode == "max" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("padding_idx with mode='max' reads the live count back to the host (forward(n_dev=) is not "
+                               "offered for max) -- not capturable in a hipGraph")
+        indices = indices.long() if indices.dtype != torch.int64 else indices
+        live, bag_offsets, n_live = _engine.bags_compact(indices.contiguous(), offsets, L, pad)
+        if mode == "max":
+            return self._forward_closed(live[:int(n_live.item())], bag_offsets, warmup, None)
+        summed = self._forward_n(live, bag_offsets, n_live)
+        return summed if mode == "sum" else TTMeanPoolFunction.apply(summed, bag_offsets)
+
+    def _forward_mode(self, indices, offsets, warmup, per_sample_weights, n_dev, closed: bool = False) -> torch.Tensor:
         """mode="mean": the sum lookup (any route) scaled per bag; mode="max": TTMaxLookupFunction on the unsplit geometry."""
         if per_sample_weights is not None:
             raise ValueError(f"per_sample_weights is only supported with mode='sum' (as in torch), not mode={self.mode!r}")
@@ -1035,7 +1150,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 raise NotImplementedError("mode='max' does not support forward(n_dev=)")
             if indices.dim() != 1 or offsets.dim() != 1:
                 raise ValueError("indices and offsets must be 1-D (the 2-D fixed-length form of nn.EmbeddingBag is not supported)")
-            indices, offsets = self._normalise(indices, offsets)
+            indices, offsets = self._normalise(indices, offsets, closed)
             if (offsets.numel() - 1) % self.num_tables != 0:
                 raise ValueError(f"offsets must describe num_tables * B bags, got {offsets.numel() - 1} bags for "
                                  f"{self.num_tables} tables")
@@ -1047,12 +1162,13 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 indices.contiguous(), offsets.contiguous(), self.optimizer, self.learning_rate, self.eps, self.sparse,
                 list(self.optimizer_state), *self.tt_cores)
         # mean: the bag lengths come from the offsets in their closing-entry form (n_dev: the caller's, which must have it)
-        bag_offsets = offsets.long() if n_dev is not None else self._normalise(indices, offsets)[1]
-        summed = self._forward_sum(indices, offsets, warmup, None, n_dev)
+        bag_offsets = offsets.long() if n_dev is not None else self._normalise(indices, offsets, closed)[1]
+        summed = self._forward_sum(indices, offsets, warmup, None, n_dev, closed)
         return TTMeanPoolFunction.apply(summed, bag_offsets.contiguous())
 
     def _forward_sum(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
-                     per_sample_weights: Optional[torch.Tensor] = None, n_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     per_sample_weights: Optional[torch.Tensor] = None, n_dev: Optional[torch.Tensor] = None,
+                     closed: bool = False) -> torch.Tensor:
         if n_dev is not None:
             if per_sample_weights is not None:  # (round 6, advisor: the weights were silently dropped on this route)
                 raise NotImplementedError("forward(n_dev=) does not take per_sample_weights")
@@ -1091,7 +1207,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 e = ev.pop((id(indices), id(offsets)), None)
                 if e is not None and e[0] is indices and e[1] is offsets and e[2] == indices._version and e[3] == offsets._version:
                     d["_pf_counted"] = True
-            indices, offsets = self._normalise(indices, offsets)
+            indices, offsets = self._normalise(indices, offsets, closed)
         if (offsets.numel() - 1) % self.num_tables != 0:
             raise ValueError(f"offsets must describe num_tables * B bags, got {offsets.numel() - 1} bags for "
                              f"{self.num_tables} tables")
@@ -1218,13 +1334,13 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
                  reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
-                 mode: str = "sum") -> None:
+                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
                          enforce_embedding_dim, device, include_last_offset, dedup, reference_exact_populate,
-                         deterministic_cache_update, mode)
+                         deterministic_cache_update, mode, padding_idx)
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # squeeze is a view both ways: `[0]` would make autograd materialise a zero [1,B,D] buffer
         # and copy the gradient into it (two extra kernels per step)

@@ -252,6 +252,34 @@ int ttx_tt_backward_rows(const ttx_geom* g, int32_t optim, int32_t D, float lear
                          float* const* tt_cores, float* const* optimizer_state, float* const* d_tt_cores,
                          const void* plan, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
 
+/* ------------------------------ padded bags: padding_idx (not in the reference) -----
+ * nn.EmbeddingBag(padding_idx=) and its 2-D fixed-length input: a ragged batch fed with static shapes, every bag padded to
+ * L slots with one index value.  ttx_bags_compact turns the padded bags into ragged bags plus a device-side live count --
+ * what ttx_lookup_prologue_n takes -- so the padding costs no contraction, is not counted in the frequency table and
+ * the step stays capturable.  A stable stream compaction by flag (indices[i] != padding_idx):
+ *
+ *   out_indices[0 .. n)    the live slots IN THEIR ORIGINAL ORDER (the order inside a bag decides a tie of the max mode and
+ *                          the order of the fp32 bag sum); out_indices[n .. nnz) = 0.  Every element has exactly one writer,
+ *                          no memset runs in front: the buffer is a function of the input alone.
+ *   out_offsets[b]         live slots in front of bag b, b < nb; out_offsets[nb] = *n_live = n.  Empty bags and bags of
+ *                          padding only give equal consecutive entries.
+ *   bags                   offsets != NULL: nb + 1 int64 entries, closing one included, offsets[0] = 0 and offsets[nb] = nnz as
+ *                          everywhere (entries are clamped to [0, nnz]); offsets == NULL: bag b is slots [b L, (b + 1) L) and
+ *                          nnz == nb L.
+ *   nnz == 0 or nb == 0    returns 0 after zeroing out_offsets (nb + 1 entries) and *n_live where those pointers are not NULL.
+ *   errors                 negative sizes, nnz >= 2^31, NULL indices / outputs / workspace, offsets == NULL with nnz != nb L,
+ *                          a workspace below ttx_bags_compact_workspace_bytes or not 8-byte aligned: -1 with ttx_last_error()
+ *                          set, before anything touches a device.
+ *   launches               one up to 32768 slots (every work-group builds the rank table of the whole batch in LDS itself);
+ *                          above that a count and a scatter launch over tiles of >= 4096 slots (at most 1024 tiles) and,
+ *                          with offsets given as an array, a third that gathers the bag starts.
+ *                          No atomics, no work-group waits on another inside a launch: bit-identical from run to run, nothing
+ *                          read back (capturable).  indices 16-byte aligned: two slots per 16-byte load. */
+size_t ttx_bags_compact_workspace_bytes(int64_t nb, int64_t nnz);
+int ttx_bags_compact(int64_t nb, int64_t nnz, const int64_t* indices, const int64_t* offsets, int64_t L, int64_t padding_idx,
+                     int64_t* out_indices, int64_t* out_offsets, int32_t* n_live, void* workspace, size_t workspace_bytes,
+                     ttx_stream_t stream);
+
 /* ----------------------------------------------- duplicate lookups -----
  * Not in the reference (which contracts every lookup on its own): a batch's lookups are mapped onto their
  * DISTINCT (table, index) pairs, the contraction runs once per pair, bag pooling gathers each lookup's row
