@@ -3,7 +3,8 @@
 run_plan_cases: geometry (T, q, ranks, p up to 3000), table count, batch, ragged / empty bags and a
 70 %-on-three-indices skew drawn at random so that every plan route (tiny / single launch / wave units / wide
 digit / table groups / multi-pass), the generic kernels' block walk of core 1 (small LDS budgets), per-table row factors (ttx_geom::p_tables) and the module's route
-(ttx_lookup_prologue) are hit; forward + dense gradients.
+(ttx_lookup_prologue) are hit; forward + dense gradients, and -- tables of one row factoring -- fused SGD and fused Adagrad from a
+non-zero state.
 run_cache_cases: the cache-live prologue (offsets -> bag rows, cache lookup, stable partition: bit-exact) and the
 cache gather / SGD scatter.
 
@@ -17,7 +18,7 @@ import torch
 
 import gen_inputs as G
 import oracle_lib as O
-from util import assert_close
+from util import RTOL, assert_adagrad_close, assert_close
 
 dev = torch.device("cuda:0")
 
@@ -129,10 +130,30 @@ def run_plan_cases(seed=0, max_cases=None, budget=None):
         out = E.tt_forward(1000, tables, B, D, p, q, r, Lt, nnz, t(idx), ri, ti, gc, plan=plan)
         grads = E.tt_dense_backward(1000, D, p, q, r, Lt, nnz, t(idx), ri, ti, t(d_out), gc, plan=plan)
         what = f"case {n}: T={T} tables={tables} p={p} q={q} r={r} B={B} nnz={nnz} walk={walk}"
-        tol = dict(rtol=5e-5, atol_scale=1e-5)  # (hot slices: thousands of terms in an order of their own; measured worst: 1.5x the default bound)
+        tol = dict(rtol=5e-5, atol_scale=1e-5)  # (hot slices: thousands of terms in an order of their own; measured worst: 2.25x the default bound, profiles/r08_tolerances.md)
         assert_close(out.cpu().numpy(), ref_out, what + " out", **tol)
         for k in range(T):
             assert_close(grads[k].cpu().numpy(), ref_g[k], what + f" grad{k}", **tol)
+        # the fused optimizers on the same route: SGD, and Adagrad from a NON-ZERO state (s = s0 + g^2 -- a zero state cannot tell that
+        # from s = g^2), against the oracle at the case's tolerance.  (Draws from a stream of their own: the cases above stay what
+        # they were.)
+        rs2 = np.random.RandomState([seed, n, 78])
+        lr, eps = float(rs2.choice([0.1, 0.02])), float(rs2.choice([1e-4, 1e-2]))
+        state0 = [(rs2.rand(*x.shape) * 2.0 * max(float((gk * gk).max()), 1e-12)).astype(np.float32) for x, gk in zip(cores, ref_g)]
+        ref_w = [x.copy() for x in cores]
+        O.tt_backward(g, O.OPTIM_SGD, B, D, lr, 0, idx, rowidx, tableidx, d_out, ref_w)
+        gw = [t(x) for x in cores]
+        E.tt_sgd_backward(1000, D, lr, p, q, r, Lt, nnz, t(idx), ri, ti, t(d_out), gw, plan=plan)
+        for k in range(T):
+            assert_close(gw[k].cpu().numpy(), ref_w[k], what + f" sgd core{k} lr={lr}", **tol)
+        ref_w, ref_s = [x.copy() for x in cores], [x.copy() for x in state0]
+        O.tt_backward(g, O.OPTIM_ADAGRAD, B, D, lr, eps, idx, rowidx, tableidx, d_out, ref_w, ref_s)
+        gw, gs = [t(x) for x in cores], [t(x) for x in state0]
+        E.tt_adagrad_backward(1000, D, lr, eps, p, q, r, Lt, nnz, t(idx), ri, ti, t(d_out), gs, gw, plan=plan)
+        for k in range(T):
+            assert_close(gs[k].cpu().numpy(), ref_s[k], what + f" adagrad state{k}", **tol)
+            assert_adagrad_close(gw[k].cpu().numpy(), ref_w[k], ref_g[k], what + f" adagrad core{k} lr={lr} eps={eps}", lr=lr, eps=eps,
+                                 state0=state0[k], scale=tol["rtol"] / RTOL)
         S = tables * max(p)
         route = "tiny" if nnz <= 1024 and E_ <= 2**32 else ("single" if S <= 256 and nnz <= 16384 else ("units" if S <= 256 else ("wide" if S <= 2048 else "multi-pass")))
         routes[route] = routes.get(route, 0) + 1

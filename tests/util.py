@@ -17,6 +17,14 @@ _WIDE = {}
 
 
 def _record_wide(what, rtol, atol_scale, err, ref, atol):
+    bound = atol + rtol * np.abs(ref)
+    dflt = ATOL_SCALE * atol / max(atol_scale, 1e-300) + RTOL * np.abs(ref)      # what the default tolerance would have allowed
+    record_wide_bounds(what, rtol, atol_scale, err, bound, dflt)
+
+
+def record_wide_bounds(what, rtol, atol_scale, err, bound, dflt):
+    """err against an elementwise bound that is wider than `dflt`, the same bound at the default tolerance (the derived bounds of
+    assert_adagrad_close(scale=) and tt_ref64.assert_state_close(scale=); rtol, atol_scale: the widened GRADIENT tolerance behind them)"""
     import atexit
     import json
     import os
@@ -25,9 +33,7 @@ def _record_wide(what, rtol, atol_scale, err, ref, atol):
     if not path:
         return
     test = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0]
-    bound = atol + rtol * np.abs(ref)
     used = float((err / bound).max()) if err.size else 0.0                       # share of the WIDENED bound used (1 = at the limit)
-    dflt = ATOL_SCALE * atol / max(atol_scale, 1e-300) + RTOL * np.abs(ref)      # what the default tolerance would have allowed
     over = float((err / dflt).max()) if err.size else 0.0                        # worst error in units of the DEFAULT bound
     if not _WIDE:
         def dump():
@@ -75,20 +81,26 @@ def adagrad_expected(cores, grads, lr=LR, eps=EPS):
     return new, state
 
 
-def assert_adagrad_close(got_w, ref_w, ref_g, what="", lr=LR, eps=EPS, state0=None):
+def assert_adagrad_close(got_w, ref_w, ref_g, what="", lr=LR, eps=EPS, state0=None, scale=1.0):
     """First Adagrad step w - lr*g/(sqrt(s0 + g^2)+eps): its derivative w.r.t. g is
     lr*(eps + s0-terms)/(|g|+eps)^2 <= lr/eps, so a gradient that is within the
     gradient tolerance (RTOL, ATOL_SCALE*max|g|) moves w by up to that factor.
     The gradient itself is checked at the tight tolerance by the dense-mode and
-    optimizer-state tests."""
+    optimizer-state tests.  state0: the state the step starts from (None: zeros).
+    scale: the factor by which the caller's GRADIENT comparison was widened beyond the
+    default (tests/test_fused_optimizer_gpu.py: a reference that is itself that far
+    from float64); the gradient's share of the bound grows with it."""
     got_w = np.asarray(got_w, dtype=np.float64)
     ref_w = np.asarray(ref_w, dtype=np.float64)
     g = np.abs(np.asarray(ref_g, dtype=np.float64))
     assert np.isfinite(got_w).all() and np.isfinite(ref_w).all(), f"{what}: non-finite values"
-    dg = ATOL_SCALE * max(float(g.max()), 1e-30) + RTOL * g
+    dg = float(scale) * (ATOL_SCALE * max(float(g.max()), 1e-30) + RTOL * g)
     denom = (np.sqrt(g * g + (0.0 if state0 is None else np.asarray(state0, dtype=np.float64))) + eps)
-    tol = RTOL * np.abs(ref_w) + 2e-7 * max(float(np.abs(ref_w).max()), 1e-30) + lr * dg * (eps + denom) / (denom * denom)
+    own = RTOL * np.abs(ref_w) + 2e-7 * max(float(np.abs(ref_w).max()), 1e-30)
+    tol = own + lr * dg * (eps + denom) / (denom * denom)
     err = np.abs(got_w - ref_w)
+    if scale > 1.0:  # (a widened comparison: into the report like assert_close's)
+        record_wide_bounds(what, RTOL * scale, ATOL_SCALE * scale, err, tol, own + lr * (dg / scale) * (eps + denom) / (denom * denom))
     bad = err > tol
     if bad.any():
         i = np.unravel_index(np.argmax(err - tol), err.shape)
