@@ -15,10 +15,12 @@ Extras beyond the reference's eleven names (used by tt_embeddings_ops.py and
 bench.py): `make_plan` (share the lookup plan between forward and backward; `dedup=True`: duplicate lookups of
 the batch share one contraction),
 `profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
-`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, and padded bags' `bags_compact`.
+`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, and `bags_merge` (the per-table
+batches of a mixed-cardinality group -> one table-major batch, one launch).
 """
 import ctypes as C
 import os
+import struct
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -167,6 +169,8 @@ def _load(path):
     L.ttx_bags_compact_workspace_bytes.restype = C.c_size_t
     L.ttx_bags_compact_workspace_bytes.argtypes = [i64, i64]
     L.ttx_bags_compact.argtypes = [i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
+    # merged bags (per-table batches -> one table-major batch)
+    L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
 
 
@@ -873,6 +877,99 @@ def bags_compact(indices: torch.Tensor, offsets: Optional[torch.Tensor], L: int,
                                    int(padding_idx), out_i.data_ptr(), out_o.data_ptr(), n_live.data_ptr(), ws.data_ptr(),
                                    ws.numel(), st))
     return out_i, out_o, n_live
+
+
+# ---- merged bags: per-table batches -> one table-major batch (include/ttx.h "merged bags") ----
+_WIDTH = {torch.int64: 8, torch.int32: 4}
+
+
+def bags_merge(indices: Sequence[torch.Tensor], offsets: Sequence[Optional[torch.Tensor]], include_last_offset: bool,
+               per_sample_weights: Optional[Sequence[Optional[torch.Tensor]]] = None,
+               padding: Optional[Sequence[Optional[int]]] = None, sentinel: int = -1
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """One batch per table -> the table-major batch of a table-batched lookup, in one launch (64 tables per launch).  Table k:
+    `indices[k]` int64 / int32, 1-D with `offsets[k]` (B bag starts, plus the closing entry when `include_last_offset`), or 2-D
+    [B, L_k] with `offsets[k] = None`; `per_sample_weights[k]` float32 of the shape of indices[k], or None for ones;
+    `padding[k]`: slots that hold it are written as `sentinel`.  -> (out_indices [N] int64, out_offsets [ntab * B + 1] int64,
+    out_weights [N] float32 -- None unless some table has weights).  No host read-back."""
+    ntab = len(indices)
+    if ntab < 1 or len(offsets) != ntab:
+        raise RuntimeError(f"tt_embeddings: bags_merge needs one (indices, offsets) pair per table, got {ntab} and {len(offsets)}")
+    if per_sample_weights is not None and all(w is None for w in per_sample_weights):
+        per_sample_weights = None
+    for name, seq in (("per_sample_weights", per_sample_weights), ("padding", padding)):
+        if seq is not None and len(seq) != ntab:
+            raise RuntimeError(f"tt_embeddings: bags_merge: {name} must have one entry per table")
+    dev = _dev(indices[0])
+    # (plain lists first, one ctypes array each at the end: this loop is host time in front of every step of a host-bound module)
+    width = _WIDTH
+    p_idx, p_off, p_w, v_nnz, v_L, v_pad, v_ib, v_ob, v_has = [], [], [], [], [], [], [], [], []
+    keep, B = [], None
+    drop = 1 if include_last_offset else 0
+    for k in range(ntab):
+        idx, off = indices[k], offsets[k]
+        ib = width.get(idx.dtype)
+        if ib is None or idx.device != dev:
+            raise RuntimeError(f"tt_embeddings: bags_merge: indices[{k}] must be int64 or int32 on {dev}, got {idx.dtype} on {idx.device}")
+        if not idx.is_contiguous():
+            idx = idx.contiguous()
+            keep.append(idx)
+        if off is None:
+            if idx.dim() != 2:
+                raise RuntimeError(f"tt_embeddings: bags_merge: indices[{k}] without offsets must be 2-D [B, L]")
+            nb, L = idx.shape
+            p_off.append(0)
+            v_ob.append(8)
+        else:
+            ob = width.get(off.dtype)
+            if idx.dim() != 1 or off.dim() != 1:
+                raise RuntimeError(f"tt_embeddings: bags_merge: indices[{k}] and offsets[{k}] must be 1-D")
+            if ob is None or off.device != dev:
+                raise RuntimeError(f"tt_embeddings: bags_merge: offsets[{k}] must be int64 or int32 on {dev}, got {off.dtype} on {off.device}")
+            if not off.is_contiguous():
+                off = off.contiguous()
+                keep.append(off)
+            nb, L = off.numel() - drop, 0
+            p_off.append(off.data_ptr())
+            v_ob.append(ob)
+        if B is None:
+            B = nb
+        if nb != B or nb < 0:
+            raise RuntimeError(f"tt_embeddings: bags_merge: every table must describe the same number of bags, got {B} and {nb}")
+        if per_sample_weights is not None:
+            w = per_sample_weights[k]
+            if w is None:
+                p_w.append(0)
+            else:
+                if w.device != dev or w.dtype != torch.float32 or w.shape != indices[k].shape:
+                    raise RuntimeError(f"tt_embeddings: bags_merge: per_sample_weights[{k}] must be float32 on {dev} with the shape "
+                                       f"of indices[{k}], got {w.dtype} {tuple(w.shape)} on {w.device}")
+                w = w.detach()
+                if not w.is_contiguous():
+                    w = w.contiguous()
+                keep.append(w)
+                p_w.append(w.data_ptr())
+        p_idx.append(idx.data_ptr())
+        v_nnz.append(idx.numel())
+        v_ib.append(ib)
+        v_L.append(L)
+        if padding is not None:
+            v = padding[k]
+            v_pad.append(0 if v is None else int(v))
+            v_has.append(0 if v is None else 1)
+    # (the host arrays as packed bytes: a ctypes array costs 4 us to build, there would be nine)
+    q, i = struct.Struct(f"{ntab}q").pack, struct.Struct(f"{ntab}i").pack
+    a_idx, a_off, a_nnz, a_L, a_ib, a_ob = q(*p_idx), q(*p_off), q(*v_nnz), q(*v_L), i(*v_ib), i(*v_ob)
+    a_w = q(*p_w) if per_sample_weights is not None else None
+    a_pad, a_has = (q(*v_pad), bytes(v_has)) if padding is not None else (None, None)
+    N = sum(v_nnz)
+    out_i = torch.empty(N, dtype=torch.int64, device=dev)
+    out_o = torch.empty(ntab * B + 1, dtype=torch.int64, device=dev)
+    out_w = torch.empty(N, dtype=torch.float32, device=dev) if per_sample_weights is not None else None
+    with _guard(dev):
+        _check(lib().ttx_bags_merge(ntab, B, drop, a_idx, a_nnz, a_ib, a_off, a_ob, a_L, a_w, a_pad, a_has, int(sentinel),
+                                    out_i.data_ptr(), out_o.data_ptr(), None if out_w is None else out_w.data_ptr(), _stream(dev)))
+    return out_i, out_o, out_w
 
 
 def profile_enable(mask: int) -> None:

@@ -390,6 +390,8 @@ class TTMaxLookupFunction(torch.autograd.Function):
                 indices: torch.Tensor, offsets: torch.Tensor, optimizer: OptimType, learning_rate: float, eps: float,
                 sparse: bool, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
         num_tables = tt_cores[0].size(0)
+        if len(tt_p_shapes) > 0 and isinstance(tt_p_shapes[0], (list, tuple)):
+            num_tables = len(tt_p_shapes)  # tables of different row factors: cores are [1, sum p, slice]
         nnz = indices.numel()
         no_cache = indices.new_empty(0)
         _, rowidx, tableidx, _, _ = _engine.preprocess_indices_sync(indices, offsets, num_tables, True, no_cache,

@@ -24,7 +24,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from tt_embeddings_ops import OptimType, TableBatchedTTEmbeddingBag, suggested_tt_shapes
+import tt_embeddings_ops as _ops
+from tt_embeddings_ops import (POOLING_MODES, OptimType, TableBatchedTTEmbeddingBag, _normalise_padding_idx,
+                               suggested_tt_shapes)
 
 
 def merge_bags(indices: Sequence[torch.Tensor], offsets: Sequence[torch.Tensor],
@@ -61,8 +63,12 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True,
-                 table_ranks: Optional[Sequence[List[int]]] = None, table_q: Optional[Sequence[List[int]]] = None) -> None:
-        """`table_q` (one factoring per table, entry by entry <= `tt_q_shapes`, every one a factoring of `embedding_dim`; round 4):
+                 table_ranks: Optional[Sequence[List[int]]] = None, table_q: Optional[Sequence[List[int]]] = None,
+                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
+        """`mode`, `padding_idx` (trailing keywords, as on the parent): nn.EmbeddingBag's pooling modes and padded batches, on the
+        parent's routes -- forward also takes the 2-D form `indices[num_tables * B, L]` with `offsets=None`.  `padding_idx` is ONE
+        value for all tables, so it has to be a row of every one of them: torch's rule against the smallest cardinality.
+        `table_q` (one factoring per table, entry by entry <= `tt_q_shapes`, every one a factoring of `embedding_dim`; round 4):
         tables whose output rows are factored DIFFERENTLY ride in the same batched lookup.  `tt_q_shapes` is then the common
         (padded) factoring the kernels run -- prod(tt_q_shapes) >= embedding_dim values per padded output row -- table k's cores are
         stored zero-padded to it like the ranks below, and forward() gathers every table's own embedding_dim values out of its
@@ -73,6 +79,10 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         common ranks.  The padding stays zero under the fused optimizers (every gradient term of a padded entry has a zero factor),
         so table k keeps behaving as a rank-`table_ranks[k]` table; what it costs is the multiply-adds on the zeros."""
         nn.Module.__init__(self)
+        if mode not in POOLING_MODES:
+            raise ValueError(f"mode must be one of {POOLING_MODES}, got {mode!r}")
+        self.mode = mode
+        self.padding_idx = _normalise_padding_idx(padding_idx, min(int(e) for e in num_embeddings))
         self.include_last_offset = bool(include_last_offset)
         if device is None:
             if not torch.cuda.is_available():
@@ -80,6 +90,11 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
             device = torch.device("cuda", torch.cuda.current_device())
         device = torch.device(device)
         nd = len(tt_ranks) + 1
+        if mode == "max" and nd != 3:
+            # (max runs ttx_tt_rows_p / ttx_tt_backward_rows on a plan with per-table row factors; the two- and four-core routes
+            #  of those two have never run on such a plan)
+            raise NotImplementedError(f"mode='max' on tables of different row factors needs three TT cores, got {nd} "
+                                      "(two- and four-core geometries: not offered)")
         Es = [int(e) for e in num_embeddings]
         assert len(Es) >= 1 and all(e > 0 for e in Es)
         ps = []
@@ -174,11 +189,12 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         r0, q, r1 = self._table_dims(k, t)
         return rows.view(-1, R0, Q, R1)[:, :r0, :q, :r1].reshape(rows.shape[0], -1)
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True,
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         res = super().forward(indices, offsets, warmup, per_sample_weights)
         if self.table_q is None:
             return res
+        # (after pooling, whatever the mode: sum, mean and max all pool column by column)
         return torch.gather(res, 2, self._cols.unsqueeze(1).expand(-1, res.size(1), -1))  # [tables, B, out_dim]
 
     def table_rows(self, t: int) -> List[torch.Tensor]:
@@ -188,6 +204,27 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
 
     def full_weight(self) -> torch.Tensor:
         raise NotImplementedError("full_weight() is per table: build a TTEmbeddingBag from table_rows()")
+
+
+PAD_SENTINEL = -1  # what a table's padding slots become in a group's merged batch: no row of any table
+
+
+class _MergeFunction(torch.autograd.Function):
+    """`bags_merge` with per_sample_weights that require a gradient: the merged weights are the tables' weights laid end to end
+    (ones where a table has none), so the backward hands every table its slice of the merged gradient."""
+
+    @staticmethod
+    def forward(ctx, indices, offsets, include_last_offset, padding, *weights):
+        idx, off, w = _ops._engine.bags_merge(indices, offsets, include_last_offset, list(weights), padding, PAD_SENTINEL)
+        ctx.mark_non_differentiable(idx, off)
+        ctx.sizes = [int(i.numel()) for i in indices]
+        ctx.shapes = [None if x is None else x.shape for x in weights]
+        return idx, off, w
+
+    @staticmethod
+    def backward(ctx, _d_idx, _d_off, d_w):
+        parts = d_w.split(ctx.sizes)
+        return (None, None, None, None) + tuple(None if s is None else p.reshape(s) for s, p in zip(ctx.shapes, parts))
 
 
 def _lookup_node(fn):
@@ -223,8 +260,12 @@ class MixedTTEmbeddingBag(nn.Module):
     captured into a hipGraph (ttx_graph.GraphedRound) the groups become parallel branches and their kernels -- each too
     small to fill the chip at DLRM batch sizes -- run side by side (scripts/bench_mixed.py).
     `tt_ranks` / `tt_q_shapes`: one list for all tables, or one list per table.
+    `mode`, `padding_idx` (trailing keywords): nn.EmbeddingBag's pooling modes and padded batches as on the uniform modules
+    (DESIGN.md 4.9 - 4.11).  `padding_idx` is None, one int, or one entry (int or None) per table, each normalised against its own
+    table's cardinality.
     forward(indices, offsets[, per_sample_weights]) takes one tensor per table (nn.EmbeddingBag call form,
-    `include_last_offset` as given to the constructor) and returns one [B, D] tensor per table."""
+    `include_last_offset` as given to the constructor; or, per table, 2-D `indices[k]` [B, L_k] with `offsets[k] = None`) and
+    returns one [B, D] tensor per table.  On GPU tensors a group's table-major batch is ONE launch (`ttx_bags_merge`)."""
 
     def __init__(self, num_embeddings: Sequence[int], embedding_dim: int, tt_ranks,
                  tt_p_shapes: Optional[Sequence[Optional[List[int]]]] = None, tt_q_shapes=None,
@@ -232,10 +273,22 @@ class MixedTTEmbeddingBag(nn.Module):
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = False,
                  streams: bool = False, fused: bool = False, pad_ranks: Optional[bool] = None,
-                 pad_q: Optional[bool] = None) -> None:
+                 pad_q: Optional[bool] = None, mode: str = "sum", padding_idx=None) -> None:
         super().__init__()
         self.num_embeddings = [int(e) for e in num_embeddings]
         n = len(self.num_embeddings)
+        if mode not in POOLING_MODES:
+            raise ValueError(f"mode must be one of {POOLING_MODES}, got {mode!r}")
+        self.mode = mode
+        # padding_idx: None, one int for all tables, or one entry (an int or None) per table -- each normalised by torch's rule
+        # against its OWN table's cardinality (-1 is every table's last row)
+        if isinstance(padding_idx, (list, tuple)):
+            if len(padding_idx) != n:
+                raise ValueError(f"padding_idx: one value, or one entry per table ({n}), got {len(padding_idx)} entries")
+            pads = list(padding_idx)
+        else:
+            pads = [padding_idx] * n
+        self.padding_idx = [_normalise_padding_idx(v, e) for v, e in zip(pads, self.num_embeddings)]
         self.embedding_dim = int(embedding_dim)
         self.include_last_offset = bool(include_last_offset)
         self._streams = None
@@ -317,27 +370,79 @@ class MixedTTEmbeddingBag(nn.Module):
                 self.groups.append(VarTableTTEmbeddingBag(
                     [self.num_embeddings[k] for k in tables], self.embedding_dim, rmax, [list(shapes[k]) for k in tables],
                     qmax, optimizer, learning_rate, eps, sparse, weight_dist, enforce_embedding_dim, device, True,
-                    [ranks[k] for k in tables] if mixed_ranks else None, [qs[k] for k in tables] if mixed_q else None))
+                    [ranks[k] for k in tables] if mixed_ranks else None, [qs[k] for k in tables] if mixed_q else None, mode))
             else:
                 self.groups.append(TableBatchedTTEmbeddingBag(
                     len(tables), max(self.num_embeddings[k] for k in tables), self.embedding_dim, list(ranks[k0]),
                     list(shapes[k0]), qs[k0], optimizer, learning_rate, eps, sparse, False, 0, 0, weight_dist,
-                    enforce_embedding_dim, device, True))
+                    enforce_embedding_dim, device, True, mode=mode))
+        # A group module takes ONE padding value, its tables may each have their own: forward() rewrites every table's padding
+        # slots to PAD_SENTINEL and the group compacts on that.  The sentinel is no valid row, so it is handed over here -- the
+        # one place -- past the constructor's normalisation, which would read -1 as "the last row".
+        for mod, tables in zip(self.groups, self.group_tables):
+            if any(self.padding_idx[k] is not None for k in tables):
+                mod.padding_idx = PAD_SENTINEL
         self._streams = [torch.cuda.Stream(device=self.groups[0].tt_cores[0].device) for _ in self.groups] \
             if streams and len(self.groups) > 1 else None
 
-    def forward(self, indices: Sequence[torch.Tensor], offsets: Sequence[torch.Tensor],
+    def _merge(self, tables: List[int], indices, offsets, per_sample_weights):
+        """the batch of one group, table-major: (indices, offsets with the closing entry, weights or None), every table's padding
+        slots rewritten to PAD_SENTINEL.  GPU tensors: one `bags_merge` launch (two from 65 tables on); CPU tensors (the tests'
+        oracle engine): `merge_bags` and torch ops."""
+        idx = [indices[k] for k in tables]
+        off = [offsets[k] for k in tables]
+        psw = None
+        d = self.__dict__  # (a module pickled before the keywords existed has neither attribute: sum, no padding)
+        if per_sample_weights is not None and any(per_sample_weights[k] is not None for k in tables):
+            if d.get("mode", "sum") != "sum":
+                raise ValueError(f"per_sample_weights is only supported with mode='sum' (as in torch), not mode={d['mode']!r}")
+            psw = [per_sample_weights[k] for k in tables]
+        pads = d.get("padding_idx")
+        pads = [None] * len(tables) if pads is None else [pads[k] for k in tables]
+        nb = set()
+        for k, i, o in zip(tables, idx, off):
+            if (i.dim() == 2) != (o is None) or i.dim() not in (1, 2):
+                raise ValueError(f"table {k}: 1-D indices with 1-D offsets, or 2-D indices [B, L] with offsets None (as in torch)")
+            nb.add(int(i.size(0)) if o is None else int(o.numel()) - (1 if self.include_last_offset else 0))
+        if len(nb) != 1:
+            raise ValueError(f"every table must describe the same number of bags, got {sorted(nb)}")
+        if psw is not None:
+            for k, i, w in zip(tables, idx, psw):
+                if w is not None and w.shape != i.shape:
+                    raise ValueError(f"table {k}: per_sample_weights must have the shape of indices")
+        has_pad = any(v is not None for v in pads)
+        if idx[0].is_cuda:
+            if psw is not None:
+                psw = [None if w is None else w.float() for w in psw]
+            if psw is not None and any(w is not None and w.requires_grad for w in psw):
+                return _MergeFunction.apply(idx, off, self.include_last_offset, pads if has_pad else None, *psw)
+            return _ops._engine.bags_merge(idx, off, self.include_last_offset, psw, pads if has_pad else None, PAD_SENTINEL)
+        entries = nb.pop() + (1 if self.include_last_offset else 0)
+        flat_i, flat_o = [], []
+        for i, o, v in zip(idx, off, pads):
+            if o is None:  # B bags of L slots
+                o = torch.arange(entries, dtype=torch.int64, device=i.device) * int(i.size(1))
+                i = i.reshape(-1)
+            i, o = i.long(), o.long()
+            flat_i.append(i if v is None else torch.where(i == v, torch.full_like(i, PAD_SENTINEL), i))
+            flat_o.append(o)
+        mi, mo = merge_bags(flat_i, flat_o, self.include_last_offset)
+        mw = None
+        if psw is not None:
+            mw = torch.cat([w.reshape(-1).float() if w is not None else torch.ones(i.numel(), device=mi.device)
+                            for w, i in zip(psw, flat_i)])
+        return mi, mo, mw
+
+    def forward(self, indices: Sequence[torch.Tensor], offsets: Sequence[Optional[torch.Tensor]],
                 per_sample_weights: Optional[Sequence[Optional[torch.Tensor]]] = None) -> List[torch.Tensor]:
+        """per table: 1-D `indices[k]` with `offsets[k]`, or 2-D `indices[k]` [B, L_k] with `offsets[k] = None` (tables may mix the
+        forms); `per_sample_weights[k]` of the shape of `indices[k]`, or None"""
         n = len(self.num_embeddings)
         assert len(indices) == n and len(offsets) == n, f"one (indices, offsets) pair per table: {n} tables"
         outs: List[Optional[torch.Tensor]] = [None] * n
         cur = torch.cuda.current_stream() if self._streams else None
         for g, (mod, tables) in enumerate(zip(self.groups, self.group_tables)):
-            idx, off = merge_bags([indices[k] for k in tables], [offsets[k] for k in tables], self.include_last_offset)
-            psw = None
-            if per_sample_weights is not None and any(per_sample_weights[k] is not None for k in tables):
-                psw = torch.cat([per_sample_weights[k].reshape(-1) if per_sample_weights[k] is not None
-                                 else torch.ones(indices[k].numel(), device=idx.device) for k in tables])
+            idx, off, psw = self._merge(tables, indices, offsets, per_sample_weights)
             if self._streams:
                 s = self._streams[g]
                 s.wait_stream(cur)

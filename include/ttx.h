@@ -280,6 +280,37 @@ int ttx_bags_compact(int64_t nb, int64_t nnz, const int64_t* indices, const int6
                      int64_t* out_indices, int64_t* out_offsets, int32_t* n_live, void* workspace, size_t workspace_bytes,
                      ttx_stream_t stream);
 
+/* ------------------------------ merged bags: per-table batches -> one table-major batch (not in the reference) -----
+ * Tables of different cardinality arrive as one (indices, bags[, weights]) batch per table (DLRM's call form); the table-batched
+ * lookup takes ONE batch, table-major.  ttx_bags_merge builds it in one launch per TTX_MAX_TABLES_MIXED tables -- concatenate,
+ * shift the bag starts, widen int32, fill in default weights, mark the padding -- with nothing read back and no pointer table
+ * copied to the device: every per-table argument below is a HOST array of ntab entries that travels by value in the kernel's
+ * argument block (64 tables take 2.6 KiB of the 4 KiB segment).
+ *
+ *   indices[k], nnz[k]     table k's slots: a device pointer (may be NULL when nnz[k] == 0) to int64, or int32 where
+ *                          index_bytes[k] == 4 (index_bytes == NULL: all int64), aligned to its element.
+ *   offsets[k]             table k's B bag starts (device pointer, int64, or int32 where offset_bytes[k] == 4; entries behind the
+ *                          first B -- the closing one of the include_last_offset form -- are not read), or NULL: B bags of L[k]
+ *                          slots each, nnz[k] == B * L[k] (the 2-D form; L[k] is ignored where offsets[k] is given).
+ *   weights                NULL: no table has weights and out_weights is not written.  Else weights[k] = table k's nnz[k] floats
+ *                          or NULL for 1.0f.
+ *   padding, has_padding   padding == NULL: none.  Else a slot of table k that equals padding[k] is written as `sentinel` where
+ *                          has_padding[k] != 0; every other slot is copied.
+ *   out_indices [N]        int64, N = sum nnz[k]: table k's slots at base_k = sum_{j<k} nnz[j], in order.
+ *   out_offsets [ntab B+1] int64: entry k B + b = base_k + min(max(start_k[b], 0), nnz[k]); the last entry = N.
+ *   out_weights [N]        float.
+ *   N == 0 or B == 0       the offsets owed are still written (at least the closing entry).
+ *   errors                 ntab < 1, N >= 2^31, a negative size, NULL where a pointer is owed, a pointer not aligned to its
+ *                          element, an element width other than 4 / 8, nnz[k] != B L[k] without offsets: -1 with
+ *                          ttx_last_error() set, before anything touches a device.
+ * Every output element has exactly one writer; no atomics, no memset, no workspace, no work-group waits on another: the
+ * buffers are a function of the inputs alone, bit-identical from run to run, and the call is capturable.  For int64 inputs
+ * without padding the result is, integer for integer, the concatenation torch would build. */
+int ttx_bags_merge(int32_t ntab, int64_t B, int32_t include_last_offset, const void* const* indices, const int64_t* nnz,
+                   const int32_t* index_bytes, const void* const* offsets, const int32_t* offset_bytes, const int64_t* L,
+                   const float* const* weights, const int64_t* padding, const uint8_t* has_padding, int64_t sentinel,
+                   int64_t* out_indices, int64_t* out_offsets, float* out_weights, ttx_stream_t stream);
+
 /* ----------------------------------------------- duplicate lookups -----
  * Not in the reference (which contracts every lookup on its own): a batch's lookups are mapped onto their
  * DISTINCT (table, index) pairs, the contraction runs once per pair, bag pooling gathers each lookup's row
