@@ -265,7 +265,8 @@ def tt_matrix_to_full(tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: 
     order = list(range(0, 2 * T, 2)) + list(range(1, 2 * T, 2))
     n_rows = int(np.prod(np.asarray(tt_p_shapes, dtype=np.int64)))
     n_cols = int(np.prod(np.asarray(tt_q_shapes, dtype=np.int64)))
-    return acc.permute(order).contiguous().reshape(n_rows, n_cols).float()
+    full = acc.permute(order).contiguous().reshape(n_rows, n_cols)
+    return full if full.dtype == torch.float64 else full.float()  # (float64 cores: a float64 table, for the tests' references)
 
 
 class TTLookupFunction(torch.autograd.Function):

@@ -4,7 +4,7 @@ run_plan_cases: geometry (T, q, ranks, p up to 3000), table count, batch, ragged
 70 %-on-three-indices skew drawn at random so that every plan route (tiny / single launch / wave units / wide
 digit / table groups / multi-pass), the generic kernels' block walk of core 1 (small LDS budgets), per-table row factors (ttx_geom::p_tables) and the module's route
 (ttx_lookup_prologue) are hit; forward + dense gradients, and -- tables of one row factoring -- fused SGD and fused Adagrad from a
-non-zero state.
+non-zero state, then forward and both fused backwards once more with per_sample_weights against the weighted float64 reference.
 run_cache_cases: the cache-live prologue (offsets -> bag rows, cache lookup, stable partition: bit-exact) and the
 cache gather / SGD scatter.
 
@@ -18,7 +18,8 @@ import torch
 
 import gen_inputs as G
 import oracle_lib as O
-from util import RTOL, assert_adagrad_close, assert_close
+import tt_ref64 as R
+from util import ATOL_SCALE, RTOL, assert_adagrad_close, assert_close
 
 dev = torch.device("cuda:0")
 
@@ -154,6 +155,60 @@ def run_plan_cases(seed=0, max_cases=None, budget=None):
             assert_close(gs[k].cpu().numpy(), ref_s[k], what + f" adagrad state{k}", **tol)
             assert_adagrad_close(gw[k].cpu().numpy(), ref_w[k], ref_g[k], what + f" adagrad core{k} lr={lr} eps={eps}", lr=lr, eps=eps,
                                  state0=state0[k], scale=tol["rtol"] / RTOL)
+        # the same backward a second time with per_sample_weights (a weight per lookup in [-0.5, 1.5), a tenth exactly 0), against
+        # the weighted float64 reference tests/tt_ref64.py -- the oracle has no weights: a route that drops the weights, or reads them
+        # in another order than the lookups', fails here whatever plan it took.  Tolerance: the DEFAULT; a comparison that misses it
+        # is looked at again under the rule of tests/test_per_sample_weights_gpu.py -- the fp32 oracle on the one-bag-per-lookup
+        # restatement of this case, run only then (it is slow), more than half a default bound from float64 itself: twice its distance,
+        # capped at (5e-5, 1e-5).  (Draws from a stream of their own again.)
+        rs3 = np.random.RandomState([seed, n, 79])
+        psw = (rs3.rand(nnz) * 2.0 - 0.5).astype(np.float32)
+        psw[rs3.rand(nnz) < 0.1] = 0.0
+        ref64 = R.forward_backward(tables, p, q, r, B, idx, rowidx, tableidx, cores, d_out, per_sample_weights=psw)
+        orc = []
+
+        def factor(which, k, ref):
+            if tables * nnz * D * 4 > 1 << 30:  # (the restated bag gradients [tables, nnz, D]: too large here -- the default stands)
+                return 1.0
+            if not orc:
+                orc.append(R.oracle_on_restatement(tables, p, q, r, B, idx, rowidx, tableidx, psw, cores, d_out, lr))
+            o = orc[0][which]
+            f, u = R.widen_factor(o if k is None else o[k], ref)
+            print(f"[fuzz] {what} weighted {('out', '', 'grad', 'sgd core')[which]}{'' if k is None else k}: oracle {u:.3f} default bounds from float64 -> bound x{f:.2f}")
+            return f
+
+        def close(got, ref, label, which, k):
+            try:
+                assert_close(got, ref, what + label)
+            except AssertionError:
+                f = factor(which, k, ref)
+                if f <= 1.0:
+                    raise
+                assert_close(got, ref, what + label, rtol=RTOL * f, atol_scale=ATOL_SCALE * f)
+
+        dpsw = t(psw)
+        out = E.tt_forward(1000, tables, B, D, p, q, r, Lt, nnz, t(idx), ri, ti, gc, plan=plan, per_sample_weights=dpsw)
+        close(out.cpu().numpy(), ref64["out"], " weighted out", 0, None)
+        gw = [t(x) for x in cores]
+        E.tt_sgd_backward(1000, D, lr, p, q, r, Lt, nnz, t(idx), ri, ti, t(d_out), gw, plan=plan, per_sample_weights=dpsw)
+        for k, e in enumerate(R.sgd_step(cores, ref64["grads"], lr)):
+            close(gw[k].cpu().numpy(), e, f" weighted sgd core{k} lr={lr}", 3, k)
+        e_w, e_s = R.adagrad_step(cores, state0, ref64["grads"], ref64["touched"], lr, eps)
+        gw, gs = [t(x) for x in cores], [t(x) for x in state0]
+        E.tt_adagrad_backward(1000, D, lr, eps, p, q, r, Lt, nnz, t(idx), ri, ti, t(d_out), gs, gw, plan=plan, per_sample_weights=dpsw)
+        for k in range(T):
+            def ada(f, k=k):
+                R.assert_state_close(gs[k].cpu().numpy(), e_s[k], ref64["grads"][k], what + f" weighted adagrad state{k}", scale=f)
+                assert_adagrad_close(gw[k].cpu().numpy(), e_w[k], ref64["grads"][k], what + f" weighted adagrad core{k} lr={lr} eps={eps}",
+                                     lr=lr, eps=eps, state0=state0[k], scale=f)
+
+            try:
+                ada(1.0)
+            except AssertionError:
+                f = factor(2, k, ref64["grads"][k])  # (the gradient's factor, as for the state and weights of the per-site file)
+                if f <= 1.0:
+                    raise
+                ada(f)
         S = tables * max(p)
         route = "tiny" if nnz <= 1024 and E_ <= 2**32 else ("single" if S <= 256 and nnz <= 16384 else ("units" if S <= 256 else ("wide" if S <= 2048 else "multi-pass")))
         routes[route] = routes.get(route, 0) + 1

@@ -7,7 +7,8 @@ The operation (table-batched, sum pooling).  A table of prod(p) rows of D = prod
 
     row[j_0, .., j_{T-1}] = G_0[i_0][:, j_0, :] @ G_1[i_1][:, j_1, :] @ .. @ G_{T-1}[i_{T-1}][:, j_{T-1}, :]        (a 1 x 1 matrix)
 
-flattened with j_0 most significant.  out[table, bag] = sum of the rows of the bag's lookups.  The gradient of a loss with
+flattened with j_0 most significant.  out[table, bag] = sum of the rows of the bag's lookups (each times its per_sample_weight,
+when weights are given).  The gradient of a loss with
 d loss / d out = d_out with respect to G_t[i_t][a, j, b] is, summed over the lookups that use slice i_t of that table,
 
     sum_{l, m} Left_t[l, a] * g[l, j, m] * Right_t[b, m]
@@ -78,14 +79,21 @@ def rowidx_from_offsets(offsets, tables):
     return bag % B, bag // B
 
 
-def forward_backward(tables, p, q, r, B, indices, rowidx, tableidx, cores, d_out=None, block_doubles=1 << 23):
-    """-> dict(out [tables, B, D], grads [T] x [shape of the core] (d_out given), touched [T] x bool[S_t]); all float64"""
+def forward_backward(tables, p, q, r, B, indices, rowidx, tableidx, cores, d_out=None, block_doubles=1 << 23, per_sample_weights=None):
+    """-> dict(out [tables, B, D], grads [T] x [shape of the core] (d_out given), touched [T] x bool[S_t]); all float64
+
+    per_sample_weights (nn.EmbeddingBag's, one per lookup): out[bag] += w_n row_n, a lookup brings w_n d_out[bag(n)] to its pair's
+    gradient, and -- d_out given -- d_psw[n] = <d_out[bag(n)], row_n> joins the results.  `touched` does not look at the weights:
+    a lookup of weight 0 still touches its slices, as in the kernels.  None: the statements below are the unweighted ones, the
+    results bit for bit what they were before the argument existed (tests/test_tt_ref64_cpu.py holds the earlier text against it)."""
     g = Geometry(tables, p, q, r)
     T, rr, qq = g.T, g.r, g.q
     idx = np.asarray(indices, dtype=np.int64)
     row = np.asarray(rowidx, dtype=np.int64)
     tb = np.asarray(tableidx, dtype=np.int64)
     nnz = idx.size
+    psw = None if per_sample_weights is None else np.asarray(per_sample_weights, dtype=np.float64).reshape(-1)
+    assert psw is None or psw.size == nnz, "one weight per lookup"
     W = g.cores2d(cores)
     out = np.zeros((tables * B, g.D))
     grads = [np.zeros_like(w) for w in W] if d_out is not None else None
@@ -93,6 +101,8 @@ def forward_backward(tables, p, q, r, B, indices, rowidx, tableidx, cores, d_out
     res = dict(out=out.reshape(tables, B, g.D), touched=touched)
     if d_out is not None:
         res["grads"] = [gr.reshape(np.asarray(c).shape) for gr, c in zip(grads, cores)]
+        if psw is not None:
+            res["d_psw"] = np.zeros(nnz)
     if nnz == 0:
         return res
     sid = g.slice_ids(idx, tb)
@@ -107,7 +117,8 @@ def forward_backward(tables, p, q, r, B, indices, rowidx, tableidx, cores, d_out
     gU = None
     if d_out is not None:
         gU = np.zeros((U, g.D))
-        np.add.at(gU, inv, np.asarray(d_out, dtype=np.float64).reshape(tables * B, g.D)[bag])
+        gbag = np.asarray(d_out, dtype=np.float64).reshape(tables * B, g.D)[bag]
+        np.add.at(gU, inv, gbag if psw is None else psw[:, None] * gbag)
     rows = np.empty((U, g.D))
     blk = max(1, int(block_doubles // max(max(g.slice), g.D)))
     for u0 in range(0, U, blk):
@@ -138,8 +149,51 @@ def forward_backward(tables, p, q, r, B, indices, rowidx, tableidx, cores, d_out
             ss = s[order]
             starts = np.flatnonzero(np.concatenate([[True], ss[1:] != ss[:-1]]))
             grads[t][ss[starts]] += np.add.reduceat(dG[order], starts, axis=0)
-    np.add.at(out, bag, rows[inv])
+    if psw is None:
+        np.add.at(out, bag, rows[inv])
+        return res
+    np.add.at(out, bag, psw[:, None] * rows[inv])
+    if d_out is not None:
+        res["d_psw"][:] = np.einsum("nd,nd->n", gbag, rows[inv])
     return res
+
+
+def per_lookup_restatement(tables, B, rowidx, tableidx, per_sample_weights, d_out=None):
+    """A weighted batch restated for an UNWEIGHTED implementation (the fp32 oracle, whose C has no weight argument): one bag per
+    lookup -- B' = nnz, rowidx' = arange(nnz), the tables as they were -- and, for the gradients, d_out'[table(n), n] =
+    w_n d_out[table(n), row(n)] (fp32, one rounding per element; rows of other tables' lookups zero).  The gradients of the cores
+    of the restated batch ARE the weighted batch's.  -> dict(B, rowidx, d_out [tables, nnz, D] float32 or None)"""
+    row = np.asarray(rowidx, dtype=np.int64)
+    tb = np.asarray(tableidx, dtype=np.int64)
+    w = np.asarray(per_sample_weights, dtype=np.float32).reshape(-1)
+    nnz = row.size
+    assert w.size == nnz
+    ar = np.arange(nnz, dtype=np.int64)
+    d2 = None
+    if d_out is not None:
+        d_out = np.asarray(d_out, dtype=np.float32)
+        d2 = np.zeros((tables, nnz, d_out.shape[-1]), dtype=np.float32)
+        d2[tb, ar] = w[:, None] * d_out.reshape(tables, B, -1)[tb, row]
+    return dict(B=nnz, rowidx=ar, d_out=d2)
+
+
+def pool_per_lookup_fp32(tables, B, rowidx, tableidx, per_sample_weights, rows_out, d_out=None):
+    """the other half of the restatement: `rows_out` [tables, nnz, D] is an unweighted fp32 forward of the one-bag-per-lookup batch
+    (row n at [table(n), n]) -- or [nnz, D], the lookups' rows themselves.  -> (out [tables, B, D]: the fp32 weighted sum out[bag(n)] += w_n row_n, lookup after lookup;
+    d_psw [nnz] = <d_out[bag(n)], row_n> in fp32, or None)"""
+    row = np.asarray(rowidx, dtype=np.int64)
+    tb = np.asarray(tableidx, dtype=np.int64)
+    w = np.asarray(per_sample_weights, dtype=np.float32).reshape(-1)
+    rows = np.asarray(rows_out, dtype=np.float32)
+    if rows.ndim == 3:
+        rows = rows[tb, np.arange(row.size)]
+    assert rows.shape[0] == row.size
+    out = np.zeros((tables * B, rows.shape[-1]), dtype=np.float32)
+    np.add.at(out, tb * B + row, w[:, None] * rows)                      # (float32 throughout: unbuffered, in lookup order)
+    d_psw = None
+    if d_out is not None:
+        d_psw = np.einsum("nd,nd->n", np.asarray(d_out, dtype=np.float32).reshape(tables, B, -1)[tb, row], rows)
+    return out.reshape(tables, B, -1), d_psw
 
 
 def sgd_step(cores, grads, lr):
@@ -169,6 +223,24 @@ def slice_mask(touched, cores):
             for m, c in zip(touched, cores)]
 
 
+def oracle_on_restatement(tables, p, q, r, B, indices, rowidx, tableidx, per_sample_weights, cores, d_out, lr):
+    """the fp32 oracle (oracle/ttx_oracle.c) on the one-bag-per-lookup restatement of a weighted case -> (out, d_psw, dense
+    gradients, cores after one SGD step).  Its rows are computed once per distinct (table, index) pair (a row depends on nothing
+    else); the SGD step is one fp32 step along its gradients."""
+    import oracle_lib as O
+
+    idx, tb = np.asarray(indices, dtype=np.int64), np.asarray(tableidx, dtype=np.int64)
+    g = O.make_geom(tables, p, q, r)
+    D, nnz = int(np.prod(q)), idx.size
+    _, first, inv = np.unique(tb * int(np.prod(np.asarray(p, dtype=np.int64))) + idx, return_index=True, return_inverse=True)
+    ar = np.arange(first.size, dtype=np.int64)
+    rows = O.tt_forward(g, first.size, D, idx[first], ar, tb[first], cores)[tb[first], ar][inv]
+    out, d_psw = pool_per_lookup_fp32(tables, B, rowidx, tb, per_sample_weights, rows, d_out)
+    rst = per_lookup_restatement(tables, B, rowidx, tb, per_sample_weights, d_out)
+    grads = O.tt_backward(g, O.OPTIM_DENSE, nnz, D, 0, 0, idx, rst["rowidx"], tb, rst["d_out"], [np.array(x, copy=True) for x in cores])
+    return out, d_psw, grads, [c - np.float32(lr) * gk for c, gk in zip(cores, grads)]
+
+
 # ---- distances in units of the project's default bound -----------------------------------------------------------------------
 def default_units(got, ref, rtol=1e-5, atol_scale=2e-6):
     """max |got - ref| / (atol_scale max|ref| + rtol |ref|): 1 = at the default bound of tests/util.py::assert_close"""
@@ -177,6 +249,16 @@ def default_units(got, ref, rtol=1e-5, atol_scale=2e-6):
         return 0.0
     bound = atol_scale * max(float(np.abs(ref).max()), 1e-30) + rtol * np.abs(ref)
     return float((np.abs(got - ref) / bound).max())
+
+
+WIDEN_CAP = 5.0  # (5e-5, 1e-5) in units of the default bound
+
+
+def widen_factor(oracle, ref):
+    """how much wider than the default a comparison against float64 may be: 1, or twice the fp32 oracle's own distance from
+    float64 on the same case when that is more than half a default bound, capped.  -> (factor, the oracle's distance)"""
+    u = default_units(oracle, ref)
+    return (1.0 if u <= 0.5 else min(2.0 * u, WIDEN_CAP)), u
 
 
 # ---- which site of the fused backward applies the update to a slice ------------------------------------------------------------
@@ -191,6 +273,22 @@ PACK_MAX_FLOATS = 256   # ... every slice at most 4 * kWave floats (and a multip
 PLAN_TINY_NNZ = 1024   # at most this many lookups: the tiny plan (hot counts unknown to the plan)
 PLAN_ONE_DIGIT = 256   # every core at most this many slices: the one-pass plans, which COUNT the hot pivot slices
 PLAN_UNITS_MAX_NNZ = 256 * 4096  # (kMbFuseU wave units of 4096: beyond, the multi-pass plan, which does not count them)
+
+# the forward's pooling dispatch (csrc/ttx_tt.hip tt_forward_impl, csrc/ttx_tt_spec.inc spec_launch_fwd)
+POOL_SPAN_MIN = 65536  # kPoolSpanMin: at most this many lookups pool in pool4_small_kernel / inside the specialised forward kernel
+SPEC_MC32 = 16         # TTX_MC32: lookups per (sub-)chunk of the q = [4,4,4], ranks [32,32] kernels; a plan chunk longer than this is walked in sub-chunks
+
+
+def pool_route(nnz, D, offsets_given, specialised, padded=False):
+    """which kernel pools the bags of ttx_tt_forward_o (16-byte aligned buffers, as torch's allocator gives): "fused" (inside
+    spec_fwd_kernel: offsets and counters given, a specialised unpadded shape, D % 4 == 0, a small batch), "pool4_small", "pool4"
+    or "pool_scalar" (pool_kernel)"""
+    if D % 4:
+        return "pool_scalar"
+    if nnz > POOL_SPAN_MIN:
+        return "pool4"
+    return "fused" if (offsets_given and specialised and not padded) else "pool4_small"
+
 
 SITES = ("packed", "float4_owner", "scalar_owner", "pivot_columns", "pivot_owner_fallback", "thin_fold", "t4_apply23")
 
