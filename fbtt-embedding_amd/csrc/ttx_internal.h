@@ -99,8 +99,6 @@ constexpr int kHotRowsPivot = TTX_HOT_PIVOT;  // chunk partials beyond which a p
 // backward's (which then skips its own), cleared by every plan build and by the fused optimizer's write to cores 2 / 3; [+5] = the
 // device-wide count of such writes (g_t4_epoch, ttx_tt.hip) when M was made: another plan's fused backward invalidates this M too.
 constexpr int kHdrT4Valid = 20;
-// hdr[kHdrGrab]: the chunk counter of bwd32_kernel's persistent work-groups (ttx_tt_spec.inc), zeroed in front of its launch
-constexpr int kHdrGrab = 32;
 struct Plan {
   int* hdr;  // [0] = number of chunks, [1] = MC, [2] = nnz, [3] = lrow valid, [8 + t] = hot slices of core t (-1: unknown), [20..25]: kHdrT4Valid
   int* sid[TTX_MAX_CORES];

@@ -1521,402 +1521,6 @@ static int spec_launch_fwd_v(const Plan& P, const CorePtrs& C, float* rows, floa
   return TTX_OK;
 }
 
-// ---- round 6, DESIGN.md 4.3 / 8.1: the backward of the benchmark shape (q = [4,4,4], ranks [32,32]) re-decomposed for large batches --
-// EIGHT lookups per wave (32 rows) on v_mfma_f32_32x32x2: every GEMM of a column tile is a chain of 16 MFMAs of 64 cycles (twice
-// the length of spec_bwd_kernel's MFMAs against the same fill and drain), every core_1 fragment read from LDS feeds 32 rows instead
-// of 16.  C/D layout (measured, scripts/probes/mfma32x32x2.hip): lane l, register i = D[row 8 (i/4) + 4 (l/32) + i%4][column l % 32]
-// -- with q0 = 4: lookup 2 (i/4) + l/32, core-0 row i % 4, so a lane holds all four rows of FOUR lookups at ONE column kk = l % 32
-// and both tail contractions run on the accumulator registers as in spec_bwd_kernel (here on the VALU).
-// A sub-chunk is 32 lookups (wave w: 8 w .. 8 w + 7); per column tile j1 (one q1 block = 32 columns of x_0):
-//   A   d x_0 = g core_2^T (registers; it does not wait for x_0) -> the wave's LDS tile
-//   G1  x_0[32 x 32] = A[32 x 32] core_1[32 x 32 of block j1]                  16 k-steps
-//   G2  d core_0[32 x 32] += d x_0[32 x 32] core_1[block j1]^T                  16 k-steps
-//   G3  d core_1[block j1][32 x 32] += A^T d x_0  over the WAVE's 32 rows        16 k-steps
-//   C   d core_2[lookup][kk][x] += x_0 g  on G1's accumulator
-// Version 3.  (v1 summed d core_1 cooperatively over the work-group's 128 rows: four barriers per sub-chunk, 357 us at 327k lookups
-// against spec_bwd_kernel's 326 -- scripts/probes/r06_bwd32_v1_cooperative.patch.)  Every LDS region but the core_1 slice is PRIVATE
-// to its wave and the wave keeps its own d core_1 (4 tiles x 16 registers) over the whole chunk: NO work-group barrier inside the
-// sub-chunk loop.  A sub-chunk is ONE stream of 192 MFMA slots written out in issue order (a sched_barrier behind every slot: the
-// compiler's own order put all MFMAs of a phase back to back and the register tail behind them): slot s of tile j1 = s / 48 --
-// t = s % 48 < 32: G1 / G2 alternating (two independent chains), under them phase A of tile j1 + 1 into the OTHER d x_0 tile, one
-// (lookup, row) item per two slots; t >= 32: G3, under it phase C of this tile, one item per slot; every MFMA's operands are read
-// from LDS four slots ahead.  The four waves' d core_1 meet in LDS once per chunk, added in wave order (fixed).
-// LDS: the core_1 slice (row stride 129) + per wave A (33), two d x_0 tiles (33), gradient rows = 76 KB: two work-groups per CU.
-// Same plan, same partial-buffer contract as spec_bwd_kernel; no atomics; fixed summation order.
-// Exact shape only, no per_sample_weights, no per-lookup last core -- everything else stays with spec_bwd_kernel.
-// TEST BUILD ONLY (libttx_hooks.so, ttx_debug_bwd32): measured slower than spec_bwd_kernel (DESIGN.md 4.3), kept with its parity tests.
-#if defined(TTX_TEST_HOOKS) && defined(TTX_SPEC_GROUP) && TTX_SPEC_GROUP == 32
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-namespace b32 {
-constexpr int LDA = 33, LDX = 33, LDB = 129, GD = 68;
-constexpr int szB = 32 * LDB, szA = 32 * LDA, szX = 32 * LDX, szG = 8 * GD;
-constexpr int oB = 0, oA = szB, oX = oA + kWaves * szA, oG = oX + kWaves * 2 * szX, used_floats = oG + kWaves * szG;
-constexpr int lds_floats = used_floats + 4;  // + the next chunk's index
-static_assert((oA % 4) == 0 && (oX % 4) == 0 && (oG % 4) == 0 && (szG % 4) == 0, "16-byte aligned regions");
-static_assert(2 * lds_floats * 4 <= 160 * 1024, "two work-groups per CU");
-#ifndef B32_EXP
-#define B32_EXP 0  // (timing experiments, wrong results: 1 = no phase A, 2 = no phase C, 4 = their a operands not from LDS, 8 = d x_0 not written, 16 = the thin cores' partial rows not stored, 32 = ... stored without the nontemporal hint)
-#endif
-#ifndef B32_AHEAD
-#define B32_AHEAD 4
-#endif
-constexpr int AHEAD = B32_AHEAD, RING = AHEAD + 1;  // MFMA operands are requested AHEAD slots before their MFMA
-}
-struct B32Recs { int n, sid0, sid2, bagrow; };
-// what a wave fetches for a sub-chunk: core-0 slices, gradient rows, last-core rows; n stays with the lane that read the record
-// (lane & 7 = lookup) until the partial rows are stored.  (The rows of the partials, Plan::ipos[.][n], are fetched at the top of the
-// sub-chunk that stores them: fetched with the record they were a dependent load in every sub-chunk's prologue -- 3,000 cycles.)
-struct B32Ops { float4 av[4], gv[2], c2[4]; int n; };
-__device__ __forceinline__ B32Recs b32_load_recs(const Plan& P, int start, int len, int w, bool has_row, const int64_t* __restrict__ rowidx, int lane) {
-  B32Recs R;
-  R.n = -1; R.sid0 = 0; R.sid2 = 0; R.bagrow = 0;
-  const int pos = 8 * w + (lane & 7);  // lane l: the record of lookup 8 w + (l & 7) (eight lanes per record: one broadcast load)
-  if (pos < len) {
-    const int4 rec = P.lrec[start + pos];
-    R.n = rec.x; R.sid0 = rec.y; R.sid2 = rec.z;
-    R.bagrow = has_row ? P.lrow[start + pos] : (int)rowidx[rec.x];
-  }
-  return R;
-}
-__device__ __forceinline__ B32Ops b32_load_ops(const B32Recs& R, const CorePtrs& C, const float* __restrict__ d_output, int table, int B, int lane) {
-  const int h = lane >> 5, c32 = lane & 31;
-  B32Ops O;
-  O.n = R.n;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {  // core-0 slices: float4 lane + 64 i of the wave's [8][128] block
-    const int lam = h + 2 * i;
-    const int n = __shfl(R.n, lam, kWave), sid0 = __shfl(R.sid0, lam, kWave);
-    O.av[i] = n >= 0 ? *(const float4*)(C.c[0] + (size_t)sid0 * 128 + 4 * c32) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {  // gradient rows: float4 lane + 64 i of [8][64]
-    const int lam = (lane >> 4) + 4 * i;
-    const int n = __shfl(R.n, lam, kWave), br = __shfl(R.bagrow, lam, kWave);
-    O.gv[i] = n >= 0 ? *(const float4*)(d_output + ((size_t)table * B + (size_t)br) * 64 + 4 * (lane & 15)) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {  // last-core rows kk = l % 32 of this lane's four lookups 2 j + l / 32
-    const int lam = 2 * j + h;
-    const int n = __shfl(R.n, lam, kWave), sid2 = __shfl(R.sid2, lam, kWave);
-    O.c2[j] = n >= 0 ? *(const float4*)(C.c[2] + (size_t)sid2 * 128 + 4 * c32) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  return O;
-}
-// order the compiler across a wave-private LDS hand-off (the hardware serves a wave's LDS instructions in issue order)
-__device__ __forceinline__ void b32_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// the two LDS operands of MFMA slot s (tile s / 48; t = s % 48: G1 on even t < 32, G2 on odd t < 32, G3 from 32)
-__device__ __forceinline__ void b32_slot_ops(int s, const float* Aw, const float* Xw, const float* Bs, int h, int c32, float& a, float& b) {
-  using namespace b32;
-  const int j1 = s / 48, t = s % 48;
-  const float* Xc = Xw + (j1 & 1) * szX;
-  if (t < 32) {
-    const int k = t >> 1;
-    if ((t & 1) == 0) { a = Aw[c32 * LDA + h + 2 * k]; b = Bs[(h + 2 * k) * LDB + j1 * 32 + c32]; }
-    else { a = Xc[c32 * LDX + h + 2 * k]; b = Bs[c32 * LDB + j1 * 32 + h + 2 * k]; }
-  } else {
-    const int k = t - 32;
-    a = Aw[(h + 2 * k) * LDA + c32]; b = Xc[(h + 2 * k) * LDX + c32];
-  }
-}
-
-// where wave v keeps its tile of another wave's q1 block for the chunk's fold (k = 0, 1, 2): its A region, its two d x_0 tiles
-__device__ __forceinline__ float* b32_fold_at(float* smem, int v, int k) {
-  using namespace b32;
-  static_assert(szA >= 1024 && szX >= 1024, "a 32 x 32 tile per region");
-  return k == 0 ? smem + oA + v * szA : smem + oX + v * 2 * szX + (k - 1) * szX;
-}
-// a position of the work-group's stream of sub-chunks: sub-chunk sc of chunk c (c >= the plan's chunk count: past the end)
-struct B32Pos { int c, sc, slice, start, len, slot; };
-
-#ifndef B32_WGS_PER_CU
-#define B32_WGS_PER_CU 2
-#endif
-__global__ __launch_bounds__(kThreads, B32_WGS_PER_CU) void bwd32_kernel(Plan P, CorePtrs C, int B, int p1, const int64_t* __restrict__ rowidx,
-                                                           const float* __restrict__ d_output, Partials PC, long long* stamps) {
-  using namespace b32;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  zero_hot_counters(PC);
-  // (test build: shader-clock stamps of wave 0 of the work-group's first chunks -- scripts/probes/r06_b32_stamps.py; the product
-  //  build passes nullptr and compiles them out)
-  // [0] entry, [2 + 4 k ..]: iteration k < 7 of the sub-chunk loop -- top, operands in LDS, stream start, stream end; [30] exit, [31] iterations
-#ifdef TTX_TEST_HOOKS
-  int iter = 0;
-#define B32STAMP(i) do { if (stamps && threadIdx.x == 0 && (i) < 32) stamps[(size_t)blockIdx.x * 32 + (i)] = clock64(); } while (0)
-#else
-  constexpr int iter = 0;
-#define B32STAMP(i) do { } while (0)
-#endif
-  B32STAMP(0);
-  const int tid = threadIdx.x, lane = lane_id(), w = tid / kWave;
-  const int h = lane >> 5, c32 = lane & 31, l4 = lane & 3;
-  float* Bs = smem + oB;
-  float* Aw = smem + oA + w * szA;
-  float* Xw = smem + oX + w * 2 * szX;
-  float* Gw = smem + oG + w * szG;
-  const float* Gh = Gw + h * GD;
-  const bool has_row = P.hdr[3] != 0;
-  const int nch = min(P.hdr[0], P.max_chunks), G = gridDim.x;
-  if ((int)blockIdx.x >= nch) return;
-  // PERSISTENT work-groups (two per CU): work-group g takes the chunks g, g + G, ... as ONE stream of 32-lookup sub-chunks.  A chunk's
-  // first sub-chunk paid four dependent trips to memory (chunk record -> lookup records -> operands, the slice) with half the CU
-  // idle: 30 % of a work-group's life at 128 lookups per chunk (stamps, version 4).  Here the records of position + 2 and the
-  // operands of position + 1 are in flight under the stream of the current position across chunk ends; at a chunk end the four
-  // waves meet twice (d core_1 folded through their own LDS regions, the next slice staged in the same interval).
-  // pr: the position whose records are being fetched (two ahead of the arithmetic); po, pc follow it one sub-chunk apart
-  // Which chunks: the first two by position (g, g + G), every later one from a counter in the plan's header (zeroed in front of the
-  // launch): with chunks dealt out round-robin the work-groups ran 14 .. 24 sub-chunks (median 20) and the launch lasted as long as
-  // the longest, 20 % idle.  Thread 0 asks for the index of chunk k + 2 when chunk k's last sub-chunk begins, leaves it in LDS in front of chunk k's
-  // fold barrier, every wave fetches that chunk's record behind the barrier (crn: the record of the chunk behind pr's).
-  int4 cr = P.chunk_rec[blockIdx.x];
-  int crn_c = (int)blockIdx.x + G;
-  int4 crn = crn_c < nch ? P.chunk_rec[crn_c] : make_int4(0, 0, 0, 0);
-  int grabbed = 0;
-  int* sh_next = (int*)(smem + used_floats);
-  B32Pos pr = {(int)blockIdx.x, 0, cr.x, cr.y, cr.z, cr.w}, pc = pr;
-  auto advance = [&]() {  // pr -> the next position
-    if ((pr.sc + 1) * 32 < pr.len) { ++pr.sc; return; }
-    pr.c = crn_c; pr.sc = 0;
-    pr.slice = crn.x; pr.start = crn.y; pr.len = crn.z; pr.slot = crn.w;
-    crn_c = 0x7fffffff;  // (refilled behind the fold barrier of the chunk pc is in)
-  };
-  auto recs_of = [&](const B32Pos& q, int lane) {
-    return b32_load_recs(P, q.start + q.sc * 32, q.c < nch ? min(32, q.len - q.sc * 32) : 0, w, has_row, rowidx, lane);
-  };
-  B32Recs rq = recs_of(pr, lane);
-  auto slice_request = [&](int slice, float4 (&bv)[4]) {  // a core_1 slice on its way to LDS: 1024 float4, four per thread
-    const float* B1 = C.c[1] + (size_t)slice * 4096;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bv[i] = *(const float4*)(B1 + 4 * (tid + kThreads * i));
-  };
-  auto slice_put = [&](const float4 (&bv)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + kThreads * i, row = e >> 5, c4 = e & 31;
-      float* dst = Bs + row * LDB + 4 * c4;
-      dst[0] = bv[i].x; dst[1] = bv[i].y; dst[2] = bv[i].z; dst[3] = bv[i].w;
-    }
-  };
-  {
-    float4 bv[4];
-    slice_request(pc.slice, bv);
-    slice_put(bv);
-  }
-  advance();  // pr: the position behind pc
-  f32x16 acc3[4];  // the wave's d core_1, one 32 x 32 tile per q1 block, over the chunk's sub-chunks
-  f32x16 zero16;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) zero16[i] = 0.f;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  // the partial rows of the sub-chunk before: stored behind the NEXT sub-chunk's prologue (a wait for that prologue's loads also
-  // waits for every store issued before it: 3,000 cycles per sub-chunk when the stores went first)
-  f32x16 da = zero16;
-  f32x4 dc2[4] = {zero4, zero4, zero4, zero4};
-  int pn = -1, ppos0 = 0, ppos2 = 0;
-  bool pending = false;
-  auto store_rows = [&](int lane) {
-    const int h = lane >> 5, c32 = lane & 31;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int lam = 2 * j + h;
-      const int n = __shfl(pn, lam, kWave), q0 = __shfl(ppos0, lam, kWave), q2 = __shfl(ppos2, lam, kWave);
-      if (n >= 0) {
-        spec_st4<!(B32_EXP & 32)>(dc2[j], PC.pc[2] + (size_t)q2 * 128 + 4 * c32);
-        float* o = PC.pc[0] + (size_t)q0 * 128 + c32;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) spec_st<!(B32_EXP & 32)>(da[4 * j + r], o + r * 32);
-      }
-    }
-  };
-#pragma unroll 1
-  while (pc.c < nch) {
-    B32STAMP(iter < 7 ? 2 + 4 * iter : 32);
-    // (the prologue, the stores and the fold compute their addresses from a lane id the compiler cannot trace: hoisted out of the loop
-    //  they went to scratch memory, and every reload -- a vector memory instruction -- made the wave wait for all loads in flight)
-    int lv = lane;
-    asm volatile("" : "+v"(lv));
-    const int hv = lv >> 5, c32v = lv & 31;
-    const bool first = pc.sc == 0, last = (pc.sc + 1) * 32 >= pc.len;
-    const bool alive = 8 * w < min(32, pc.len - pc.sc * 32);  // a wave behind the end of a partial sub-chunk has nothing to add
-    if (first) {  // ---- a chunk begins: its core_1 slice is in LDS (the first: above; later ones: behind the previous chunk's fold)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc3[t] = zero16;
-      __syncthreads();  // the slice is staged (and the previous chunk's fold has left the waves' regions)
-    }
-    // (asked when the chunk's LAST sub-chunk begins, read in front of its fold: asked a chunk earlier, the work-groups were committed
-    //  to two chunks each when the counter ran out, and finished up to 300,000 cycles apart)
-    if (last && tid == 0) grabbed = atomicAdd(&P.hdr[kHdrGrab], 1);
-    // the sub-chunk's operands (its records arrived under the previous stream).  NOT requested a sub-chunk ahead: their 41 registers
-    // beside the stream's sent values to scratch memory whose reloads -- vector memory instructions -- waited for every load in
-    // flight, 10,000 cycles per sub-chunk; this wait (one trip to L2) is covered by the SIMD's other wave
-    const B32Ops nxt = b32_load_ops(rq, C, d_output, pc.slice / p1, B, lv);
-    f32x4 c2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c2[j] = (f32x4){nxt.c2[j].x, nxt.c2[j].y, nxt.c2[j].z, nxt.c2[j].w};
-    const int cn = nxt.n;
-    b32_wave_sync();  // the previous sub-chunk's reads of the wave's regions are issued
-    if (alive) {
-      // ---- A and the gradient rows into the wave's regions (rows of a missing lookup: zeros)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int lam = hv + 2 * i, a = c32v >> 3, k = 4 * (c32v & 7);
-        float* dst = Aw + (4 * lam + a) * LDA + k;
-        dst[0] = nxt.av[i].x; dst[1] = nxt.av[i].y; dst[2] = nxt.av[i].z; dst[3] = nxt.av[i].w;
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) *(float4*)(Gw + ((lv >> 4) + 4 * i) * GD + 4 * (lv & 15)) = nxt.gv[i];
-    }
-    B32STAMP(iter < 7 ? 3 + 4 * iter : 32);
-    if (pending) { if (!(B32_EXP & 16)) store_rows(lv); pending = false; }  // (a stream in front of the next wait for loads, their registers free for those)
-    const B32Pos pnext = pr;
-    auto request_next = [&]() {  // the next position's records
-      if (pr.c < nch) rq = recs_of(pr, lv);
-    };
-    if (!alive) request_next();
-    if (alive) {
-    b32_wave_sync();
-    // Both register contractions run on v_mfma_f32_4x4x1 (sixteen 4 x 4 outer products over blocks of four lanes: D[lane kk][reg i] +=
-    // a[lane i of the block] b[lane kk]; 8 cycles for 256 multiply-adds): a VALU instruction does NOT run under an MFMA of its SIMD
-    // on this hardware (scripts/probes/mfma_rate.hip: every v_fma between two MFMAs adds its 4+ cycles; LDS reads and writes do not).
-    // The four lanes of a block hold four columns kk of ONE lookup:
-    //   phase A  d x_0[row r][kk] = sum_x g[r][x] core_2[kk][x]:  per lookup four MFMAs (x), a = g[r = lane % 4][x], b = core_2[kk][x]
-    //   phase C  d core_2[kk][x] += sum_r x_0[r][kk] g[r][x]:     per lookup four MFMAs (r), a = g[r][x = lane % 4], b = x_0[r][kk] (GEMM 1's register)
-    // ---- phase A of tile 0 (the only one that is not under the 32 x 32 MFMAs)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4 g = *(const f32x4*)(Gh + 2 * j * GD + l4 * 16);
-      f32x4 dxv = zero4;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) dxv = mfma1(g[x], c2[j][x], dxv);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Xw[(8 * j + 4 * h + r) * LDX + c32] = dxv[r];
-    }
-    b32_wave_sync();
-    f32x16 acc = zero16;
-    da = zero16;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dc2[j] = zero4;
-    float oa[RING], ob[RING];
-#pragma unroll
-    for (int u = 0; u < AHEAD; ++u) b32_slot_ops(u, Aw, Xw, Bs, h, c32, oa[u], ob[u]);
-    f32x4 gAc = zero4, gAn = *(const f32x4*)(Gh + l4 * 16 + 4), dxv = zero4;  // gAn: phase A of tile 1, lookup 0
-    float gCr[3] = {0.f, 0.f, 0.f};
-    __builtin_amdgcn_sched_barrier(0);
-    const int cpos0 = cn >= 0 ? P.ipos[0][cn] : 0, cpos2 = cn >= 0 ? P.ipos[2][cn] : 0;  // (used behind the stream)
-    request_next();
-    B32STAMP(iter < 7 ? 4 + 4 * iter : 32);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j1 = 0; j1 < 4; ++j1)
-#pragma unroll
-    for (int t = 0; t < 48; ++t) {
-      const int sl = j1 * 48 + t;
-      if (t == 0) b32_wave_sync();  // this tile's d x_0 was written under the previous tile
-      if (sl + AHEAD < 192) b32_slot_ops(sl + AHEAD, Aw, Xw, Bs, h, c32, oa[(sl + AHEAD) % RING], ob[(sl + AHEAD) % RING]);
-      const float a = oa[sl % RING], b = ob[sl % RING];
-      if (t < 32) {
-        if ((t & 1) == 0) acc = mfma32(a, b, t == 0 ? zero16 : acc);
-        else da = mfma32(a, b, da);
-        if (j1 < 3 && (t & 1) && !(B32_EXP & 1)) {  // phase A of tile j1 + 1: item t / 2 = (lookup j, x)
-          float* Xn = Xw + ((j1 + 1) & 1) * szX;
-          const int it = t >> 1, j = it >> 2, x = it & 3;
-          if (x == 0) gAc = gAn;
-          if (x == 1 && j < 3 && !(B32_EXP & 4)) gAn = *(const f32x4*)(Gh + 2 * (j + 1) * GD + l4 * 16 + (j1 + 1) * 4);  // the next lookup's, three items ahead
-          dxv = mfma1(gAc[x], c2[j][x], x == 0 ? zero4 : dxv);
-          if (x == 3 && !(B32_EXP & 8)) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Xn[(8 * j + 4 * h + r) * LDX + c32] = dxv[r];
-          }
-        }
-        if (t >= 30 && !(B32_EXP & 6)) gCr[(t - 30) % 3] = Gh[2 * ((t - 30) & 3) * GD + ((t - 30) >> 2) * 16 + j1 * 4 + l4];  // phase C, two slots ahead
-      } else {
-        acc3[j1] = mfma32(a, b, acc3[j1]);
-        if (!(B32_EXP & 2)) {  // phase C of this tile: item t - 32 = (row r, lookup j) -- four independent accumulators in turn
-          const int it = t - 32, j = it & 3, r = it >> 2;
-          if (it + 2 < 16 && !(B32_EXP & 4)) gCr[(it + 2) % 3] = Gh[2 * ((it + 2) & 3) * GD + ((it + 2) >> 2) * 16 + j1 * 4 + l4];
-          dc2[j] = mfma1(gCr[it % 3], acc[4 * j + r], dc2[j]);
-        }
-        if (t == 44 && j1 < 2 && !(B32_EXP & 5)) gAn = *(const f32x4*)(Gh + l4 * 16 + (j1 + 2) * 4);  // phase A of the tile after the next, lookup 0
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    B32STAMP(iter < 7 ? 5 + 4 * iter : 32);
-    pn = cn; ppos0 = cpos0; ppos2 = cpos2;
-    pending = true;
-    }
-    if (last) {
-      // ---- the chunk ends: wave v leaves its tiles of the OTHER waves' q1 blocks in its own LDS regions (A, both d x_0 tiles:
-      // 3 x 1024 floats of its 3168), wave w adds tile w in wave order and stores the chunk's pivot partial; the next chunk's slice
-      // is requested and goes to LDS behind the fold
-      const bool more = pnext.c < nch;
-      if (tid == 0) *sh_next = 2 * G + grabbed;
-      b32_wave_sync();
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (t != w) {
-          float* dst = b32_fold_at(smem, w, t - (t > w ? 1 : 0)) + lv;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dst[i * kWave] = acc3[t][i];
-        }
-      __syncthreads();
-      crn_c = *sh_next;
-      crn = crn_c < nch ? P.chunk_rec[crn_c] : make_int4(0, 0, 0, 0);
-      float* pc1 = PC.pc[1] + (size_t)pc.slot * 4096 + 4 * hv * 128 + w * 32 + c32v;
-      auto fold = [&](auto W) {  // wave W: its own tile from registers, the others' from their regions, added in wave order
-        constexpr int ww = decltype(W)::value;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          float v = 0.f;
-#pragma unroll
-          for (int v4 = 0; v4 < kWaves; ++v4) {
-            const float x = v4 == ww ? acc3[ww][i] : b32_fold_at(smem, v4, ww - (ww > v4 ? 1 : 0))[i * kWave + lv];
-            v = v4 == 0 ? x : v + x;
-          }
-          spec_st<true>(v, pc1 + (8 * (i / 4) + (i % 4)) * 128);
-        }
-      };
-      if (w == 0) fold(std::integral_constant<int, 0>{});
-      else if (w == 1) fold(std::integral_constant<int, 1>{});
-      else if (w == 2) fold(std::integral_constant<int, 2>{});
-      else fold(std::integral_constant<int, 3>{});
-      if (more) {  // the next chunk's slice (every wave is behind its last read of the old one: the barrier above).  Requested HERE:
-        float4 bv[4];  // in front of the fold its sixteen registers went to scratch memory, a wait for memory behind every load
-        slice_request(pnext.slice, bv);
-        slice_put(bv);
-      }
-      // (the second barrier is the one at the top of the next chunk; a work-group behind its last chunk leaves)
-    }
-#ifdef TTX_TEST_HOOKS
-    ++iter;
-#endif
-    pc = pnext;
-    advance();
-  }
-  if (pending) store_rows(lane);
-  B32STAMP(30);
-#ifdef TTX_TEST_HOOKS
-  if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 32 + 31] = iter;
-#endif
-#undef B32STAMP
-}
-static bool bwd32_on() { return g_bwd32_mc != 0; }
-static int bwd32_launch(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx, const float* d_output,
-                        const Partials& PC, hipStream_t st) {
-  const size_t lds = b32::lds_floats * sizeof(float);
-  const int rc = allow_dynamic_lds((const void*)bwd32_kernel, (int)lds);
-  if (rc) return rc;
-  TTX_HIP(hipMemsetAsync(P.hdr + kHdrGrab, 0, sizeof(int), st));  // the chunk counter of the persistent work-groups
-  hipLaunchKernelGGL(bwd32_kernel, dim3(std::min(P.max_chunks, B32_WGS_PER_CU * device_cus())), dim3(kThreads), lds, st, P, C, B, d.p[1], rowidx, d_output, PC,
-                     g_stamps);
-  TTX_HIP(hipGetLastError());
-  return TTX_OK;
-}
-#endif
-
 template <class S, bool MULTI, bool PAD = false>
 static int spec_launch_bwd_v(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx,
                              const float* d_output, const Partials& PC, const RealDims& R, hipStream_t st) {
@@ -1964,14 +1568,6 @@ static int spec_launch_fwd(const Plan& P, const CorePtrs& C, float* rows, float*
 template <class S>
 static int spec_launch_bwd(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx,
                            const float* d_output, const Partials& PC, bool pad, const RealDims& R, hipStream_t st) {
-#if defined(TTX_TEST_HOOKS) && defined(TTX_SPEC_GROUP) && TTX_SPEC_GROUP == 32
-  if constexpr (S::R1 == 32 && S::Q1 == 4 && S::R2 == 32 && S::Q2 == 4 && S::Q0 == 4) {
-    // (test build, ttx_debug_bwd32: eight lookups per wave on v_mfma_f32_32x32x2 for the sub-chunked plans of large batches)
-    if (bwd32_on() && !pad && P.MC > S::MC && !PC.psw && !PC.tableidx && !R.c2n &&
-        (((uintptr_t)C.c[0] | (uintptr_t)C.c[1] | (uintptr_t)C.c[2] | (uintptr_t)d_output | (uintptr_t)PC.pc[2]) & 15) == 0)
-      return bwd32_launch(d, P, C, B, rowidx, d_output, PC, st);
-  }
-#endif
   if constexpr (S::SUB) {
     if (P.MC > S::MC)
       return pad ? spec_launch_bwd_v<S, true, true>(d, P, C, B, rowidx, d_output, PC, R, st)
