@@ -15,7 +15,8 @@ Extras beyond the reference's eleven names (used by tt_embeddings_ops.py and
 bench.py): `make_plan` (share the lookup plan between forward and backward; `dedup=True`: duplicate lookups of
 the batch share one contraction),
 `profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
-`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, and `bags_merge` (the per-table
+`bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, the unpooled lookup's `rows_expand` /
+`rows_collect`, and `bags_merge` (the per-table
 batches of a mixed-cardinality group -> one table-major batch, one launch).
 """
 import ctypes as C
@@ -166,6 +167,10 @@ def _load(path):
     L.ttx_bags_compact_workspace_bytes.restype = C.c_size_t
     L.ttx_bags_compact_workspace_bytes.argtypes = [i64, i64]
     L.ttx_bags_compact.argtypes = [i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
+    # unpooled rows at padded positions (TTEmbedding's padding_idx) and the plan of a device-side count
+    L.ttx_rows_expand.argtypes = [i64, i32, vp, vp, vp, vp]
+    L.ttx_rows_collect.argtypes = [i64, i32, vp, vp, vp, vp]
+    L.ttx_plan_build_n.argtypes = [G, i64, vp, vp, vp, vp, vp, sz, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
@@ -343,13 +348,29 @@ class DedupPlan(Plan):
 
 
 def make_plan(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, nnz, indices, tableidx, rowidx=None,
-              dedup: bool = False) -> Optional[Plan]:
+              dedup: bool = False, n_dev: Optional[torch.Tensor] = None) -> Optional[Plan]:
+    """`n_dev` (trailing keyword): one int32 on the device, the number of LEADING entries of indices / tableidx / rowidx to plan
+    (<= nnz, which then only sizes the plan: ttx_plan_build_n) -- no host read-back of the count."""
     if nnz == 0:
         return None
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
     dev = _dev(indices)
     indices, tableidx = _i64(indices, "indices"), _i64(tableidx, "tableidx")
     L = lib()
+    if n_dev is not None:
+        if dedup:
+            raise RuntimeError("tt_embeddings: make_plan(dedup=True) does not take a device-side count")
+        if n_dev.dtype != torch.int32 or n_dev.numel() != 1 or n_dev.device != dev:
+            raise RuntimeError(f"tt_embeddings: n_dev must be one int32 on {dev}, got {n_dev.dtype} x {n_dev.numel()} on {n_dev.device}")
+        if indices.numel() < nnz or tableidx.numel() < nnz or (rowidx is not None and rowidx.numel() < nnz):
+            raise RuntimeError("tt_embeddings: nnz exceeds the index tensors")
+        nb = L.ttx_plan_bytes(C.byref(g), nnz)
+        buf = torch.empty(nb, dtype=torch.uint8, device=dev)
+        with _guard(dev):
+            _check(L.ttx_plan_build_n(C.byref(g), nnz, n_dev.data_ptr(), indices.data_ptr(), tableidx.data_ptr(),
+                                      None if rowidx is None else _i64(rowidx, "rowidx").data_ptr(), buf.data_ptr(), nb,
+                                      _stream(dev)))
+        return Plan(buf, nnz, (num_tables, tuple(tt_p_shapes), tuple(tt_q_shapes), tuple(tt_ranks)))
     if dedup:
         db = L.ttx_dedup_bytes(C.byref(g), nnz)
         if db:  # (0: more than 16384 lookups or a key space beyond 2^32 -- the plain plan gives the same results)
@@ -874,6 +895,40 @@ def bags_compact(indices: torch.Tensor, offsets: Optional[torch.Tensor], L: int,
                                    int(padding_idx), out_i.data_ptr(), out_o.data_ptr(), n_live.data_ptr(), ws.data_ptr(),
                                    ws.numel(), st))
     return out_i, out_o, n_live
+
+
+# ---- unpooled rows at padded positions: nn.Embedding(padding_idx=) (include/ttx.h "unpooled rows at padded positions") ----
+def _rank_rows(rank: torch.Tensor, x: torch.Tensor, name: str):
+    dev = _dev(x)
+    rank, x = _i64(rank, "rank"), _f32(x, name)
+    n = rank.numel() - 1
+    if rank.device != dev or n < 0 or x.dim() != 2 or x.size(0) != n:
+        raise RuntimeError(f"tt_embeddings: rank must hold n + 1 entries on {dev} for {name} [n, D], got {rank.numel()} on "
+                           f"{rank.device} and {tuple(x.shape)}")
+    return dev, rank, x, n
+
+
+def rows_expand(rank: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i, :] = rows[rank[i], :] where position i is live (rank[i + 1] > rank[i]), exact zeros elsewhere.  rank [n + 1] is
+    bags_compact's out_offsets of n one-slot bags; rows / out [n, D].  Every element of `out` is written."""
+    dev, rank, rows, n = _rank_rows(rank, rows, "rows")
+    if out is None:
+        out = torch.empty_like(rows)
+    elif out.shape != rows.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"tt_embeddings: out must be a contiguous float32 {tuple(rows.shape)} on {dev}")
+    with _guard(dev):
+        _check(lib().ttx_rows_expand(n, rows.size(1), rank.data_ptr(), rows.data_ptr(), out.data_ptr(), _stream(dev)))
+    return out
+
+
+def rows_collect(rank: torch.Tensor, d_out: torch.Tensor) -> torch.Tensor:
+    """d_rows[rank[i], :] = d_out[i, :] for the live positions i: the gradient rows in compacted order.  -> d_rows [n, D], whose
+    rows at and beyond rank[n] are not written (the plan's live count keeps the backward away from them)."""
+    dev, rank, d_out, n = _rank_rows(rank, d_out, "d_out")
+    d_rows = torch.empty_like(d_out)
+    with _guard(dev):
+        _check(lib().ttx_rows_collect(n, d_out.size(1), rank.data_ptr(), d_out.data_ptr(), d_rows.data_ptr(), _stream(dev)))
+    return d_rows
 
 
 # ---- merged bags: per-table batches -> one table-major batch (include/ttx.h "merged bags") ----

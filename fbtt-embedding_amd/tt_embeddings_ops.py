@@ -28,6 +28,8 @@ Deliberate differences (each is a superset or a fix):
     TTMeanPoolFunction / TTMaxLookupFunction below);
   * nn.EmbeddingBag's padded batches: ctor keyword `padding_idx` and the 2-D fixed-length input `indices[N, L]` with
     `offsets=None`; the padding is dropped on the device (`bags_compact`) in front of the lookup;
+  * nn.Embedding's unpooled lookup: the module `TTEmbedding` (one row per index of an index tensor of any shape, `padding_idx`;
+    TTRowsLookupFunction below), on the ctypes route;
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -425,6 +427,82 @@ class TTMaxLookupFunction(torch.autograd.Function):
         grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, ctx.D, 0.0, 0.0, p, q, ranks, ctx.nnz, indices, tableidx, d_rows,
                                          cores, None, ctx.plan)
         return tuple(head + list(grads))
+
+
+
+class TTRowsLookupFunction(torch.autograd.Function):
+    """The unpooled lookup (TTEmbedding, nn.Embedding's semantics): one row per position, no pooling launch, no bag rows.  The
+    contraction runs off a plan built without bag rows (as in TTMaxLookupFunction) and writes the output buffer [N, D]
+    itself; backward is the per-lookup backward / fused optimizer on the gradient rows as they come.  With `rank` (the
+    positions compacted by bags_compact as N one-slot bags: `indices` holds the live ones first, `n_dev` their number on the
+    device) only the live lookups are planned, contracted and trained; rows_expand / rows_collect carry the rows between the
+    compacted order and the positions.  `parts` = k > 1: the geometry handed in is the core-0 row split's, `indices` hold the k
+    part lookups of every position and a rows buffer [N, D] IS the parts' [k N, D / k].  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, N: int, D: int, parts: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
+                indices: torch.Tensor, rank: Optional[torch.Tensor], n_dev: Optional[torch.Tensor], optimizer: OptimType,
+                learning_rate: float, eps: float, sparse: bool, optimizer_state: List[torch.Tensor],
+                *tt_cores: torch.Tensor) -> torch.Tensor:
+        k = max(1, parts)
+        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
+        ctx.N, ctx.D, ctx.k = N, D, k
+        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
+        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        if N == 0:
+            ctx.plan = None
+            return tt_cores[0].new_empty((0, D))
+        tableidx = torch.zeros_like(indices)  # (one table)
+        plan = _engine.make_plan(1, tt_p_shapes, tt_q_shapes, tt_ranks, k * N, indices, tableidx, n_dev=n_dev)  # (no bag rows)
+        rows = _engine.tt_rows_p(1, D // k, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, list(tt_cores), plan)
+        ctx.plan = plan
+        ctx.save_for_backward(indices, tableidx, rank)
+        rows = rows.view(N, D)
+        return rows if rank is None else _engine.rows_expand(rank, rows)
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        cores = list(ctx.tt_cores)
+        head: List[Optional[torch.Tensor]] = [None] * 14
+        if ctx.N == 0:  # an empty batch: nothing to train, zero dense gradients
+            return tuple(head + [None if ctx.sparse else torch.zeros_like(c) for c in cores])
+        indices, tableidx, rank = ctx.saved_tensors
+        p, q, ranks = ctx.geometry
+        N, D, k = ctx.N, ctx.D, ctx.k
+        d_rows = d_output.contiguous().view(N, D)
+        if rank is not None:
+            d_rows = _engine.rows_collect(rank, d_rows)
+        d_rows = d_rows.view(k * N, D // k)
+        if ctx.sparse:
+            if ctx.optimizer in _SGD_LIKE:
+                _engine.tt_backward_rows(_engine.OPTIM_SGD, D // k, ctx.learning_rate, 0.0, p, q, ranks, k * N, indices, tableidx,
+                                         d_rows, cores, None, ctx.plan)
+            else:
+                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, D // k, ctx.learning_rate, ctx.eps, p, q, ranks, k * N, indices,
+                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
+            return tuple(head + [None] * len(cores))
+        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, D // k, 0.0, 0.0, p, q, ranks, k * N, indices, tableidx, d_rows,
+                                         cores, None, ctx.plan)
+        return tuple(head + list(grads))
+
+
+class _RowsAtPositionsFunction(torch.autograd.Function):
+    """rows_expand / rows_collect around a lookup that returned the rows of the live positions only (TTEmbedding's dedup route
+    with padding_idx, where the live count n has been read back): rows [n, D] -> out [N, D], zeros at the padding."""
+
+    @staticmethod
+    def forward(ctx, rows: torch.Tensor, rank: torch.Tensor) -> torch.Tensor:
+        ctx.save_for_backward(rank)
+        ctx.n = rows.size(0)
+        N = rank.numel() - 1
+        full = rows.new_empty((N, rows.size(1)))  # (rows_expand reads the rows of live positions only: the first n)
+        full[:ctx.n].copy_(rows)
+        return _engine.rows_expand(rank, full)
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        (rank,) = ctx.saved_tensors
+        return _engine.rows_collect(rank, d_output.contiguous())[:ctx.n], None
 
 
 # --------------------------------------------------------------------------- #
@@ -1353,3 +1431,105 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
         if e is not None and e[0]() is out:  # (the lookup's own node: backward() of the view is backward() of the node)
             _direct_register(res, e[1])
         return res
+
+
+class TTEmbedding(TTEmbeddingBag):
+    """Not in the reference: the UNPOOLED lookup, `nn.Embedding` on a TT table.  `emb(indices)` takes int64 / int32 indices of
+    any shape (0-D .. n-D) and returns `indices.shape + (D,)` float32 = `F.embedding(indices, W0)`, W0 = full_weight() with row
+    `padding_idx` zeroed: padding positions are exact zeros, receive no gradient and cost no contraction (they are dropped on
+    the device in front of the lookup and put back behind it; a TT table holds no independent padding row, see
+    TTEmbeddingBag).  Gradients as in the bag modules: `sparse=True` applies the fused SGD / Adagrad inside backward,
+    `sparse=False` leaves dense gradients on `tt_cores[t].grad`.  Parameters, buffers and state_dict() are those of
+    `TTEmbeddingBag(use_cache=False)` of the same geometry: a checkpoint loads in either direction.
+
+    Routes, all without a host synchronisation unless noted: plain -- a plan without bag rows, the contraction
+    straight into the output buffer, the per-lookup backward; padding_idx -- bags_compact over one-slot bags, the plan of the
+    device-side live count, rows_expand / rows_collect; q0 > 4 with an exact split -- the part lookups of the core-0 row split,
+    a rows buffer [N, D] being the parts' [k N, D / k]; dedup=True -- the bag module's duplicate-sharing sequence with one bag per
+    position (with padding_idx the live count is read back: not capturable); CPU tensors -- the bag module's reference-shaped
+    route, one bag per live position (what the tests' oracle engine runs).
+    No cache, no table batching, no prefetch, no C++ node, no max_norm / scale_grad_by_freq."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, tt_ranks: List[int],
+                 tt_p_shapes: Optional[List[int]] = None, tt_q_shapes: Optional[List[int]] = None,
+                 optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
+                 sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
+                 device: Optional[torch.device] = None, padding_idx: Optional[int] = None, dedup: bool = False) -> None:
+        super().__init__(num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer, learning_rate, eps,
+                         sparse, use_cache=False, weight_dist=weight_dist, enforce_embedding_dim=enforce_embedding_dim,
+                         device=device, include_last_offset=True, dedup=bool(dedup), mode="sum", padding_idx=padding_idx)
+
+    def prefetch(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> bool:
+        return False  # (no prologue to plan ahead: there are no bags)
+
+    def prefetch_many(self, batches) -> bool:
+        return False
+
+    def _bag_rows(self, live: torch.Tensor) -> torch.Tensor:
+        """the bag module's sum route with one bag per lookup -> [n, D] (CPU tensors, duplicate sharing)"""
+        n = live.numel()
+        return self._forward_sum(live, self._fixed_offsets(live.device, n, 1), closed=True).view(n, self.embedding_dim)
+
+    def forward(self, indices: torch.Tensor) -> torch.Tensor:  # noqa: D102 -- see the class
+        if indices.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"indices must be int64 or int32, got {indices.dtype}")
+        shape, D = tuple(indices.shape), self.embedding_dim
+        flat = indices.reshape(-1)
+        flat = flat.long() if flat.dtype != torch.int64 else flat
+        flat = flat if flat.is_contiguous() else flat.contiguous()
+        N = flat.numel()
+        pad = self.__dict__.get("padding_idx")
+        use_state = self.sparse and self.optimizer not in _SGD_LIKE
+        p, q, ranks = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks
+        if N == 0:
+            out = TTRowsLookupFunction.apply(0, D, 1, p, q, ranks, flat, None, None, self.optimizer, self.learning_rate, self.eps,
+                                             self.sparse, list(self.optimizer_state), *self.tt_cores)
+            return out.view(shape + (D,))
+        if not flat.is_cuda:
+            # the tests' oracle engine: the bag module's reference-shaped route with one bag per live position, the padding
+            # dropped (and the rows put back) with torch ops
+            if pad is None:
+                return self._bag_rows(flat).view(shape + (D,))
+            keep = torch.nonzero(flat != pad).flatten()
+            out = torch.zeros((N, D), dtype=torch.float32, device=flat.device)
+            if keep.numel() == 0:
+                out = out + sum(c.sum() for c in self.tt_cores) * 0.0  # (zero dense gradients, as an empty batch gives)
+            else:
+                out = out.index_put((keep,), self._bag_rows(flat[keep].contiguous()))
+            return out.view(shape + (D,))
+        if self.dedup:
+            # duplicate positions share one contraction: the bag module's sequence (make_plan(dedup=True), ttx_tt_forward_dd /
+            # _backward_dd) with B = N bags of one lookup; a batch ttx_dedup_bytes refuses takes the plain plan there
+            if pad is None:
+                return self._bag_rows(flat).view(shape + (D,))
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TTEmbedding(dedup=True, padding_idx=): the live count is read back to the host to size the "
+                                   "duplicate map -- not capturable in a hipGraph on this route")
+            live, rank, n_live = _engine.bags_compact(flat, None, 1, pad)
+            n = int(n_live.item())
+            if n == 0:
+                out = TTRowsLookupFunction.apply(0, D, 1, p, q, ranks, flat[:0], None, None, self.optimizer, self.learning_rate,
+                                                 self.eps, self.sparse, list(self.optimizer_state), *self.tt_cores)
+                return (torch.zeros((N, D), dtype=torch.float32, device=flat.device) + out.sum()).view(shape + (D,))
+            return _RowsAtPositionsFunction.apply(self._bag_rows(live[:n].contiguous()), rank).view(shape + (D,))
+        k = self.__dict__.get("_split0", 0) if not self.__dict__.get("_pad0", 0) else 0
+        k = k if k > 1 else 1
+        rank = n_dev = None
+        if pad is not None:
+            flat, rank, n_dev = _engine.bags_compact(flat, None, 1, pad)
+        cores, state = list(self.tt_cores), list(self.optimizer_state) if use_state else []
+        if k > 1:
+            # q0 = k q0': k part lookups per position in the table [k p0, p1, p2] x [q0', q1, q2] (views of core 0 and its
+            # optimizer state: the same memory) -- position n's parts are lookups k n .. k n + k - 1, their rows of D / k columns
+            # ARE row n of [N, D]; of a compacted batch the first k n_live part lookups are the live ones
+            flat, _ = _engine.split0_expand(flat, self._fixed_offsets(flat.device, N, 1), k, p[1] * p[2])
+            if n_dev is not None:
+                n_dev = n_dev * k
+            c0 = cores[0]
+            cores[0] = c0.view(1, k * p[0], c0.size(2) // k)
+            if use_state:
+                state[0] = state[0].view(1, k * p[0], state[0].size(2) // k)
+            p, q = [k * p[0], p[1], p[2]], [q[0] // k, q[1], q[2]]
+        out = TTRowsLookupFunction.apply(N, D, k, p, q, ranks, flat, rank, n_dev, self.optimizer, self.learning_rate, self.eps,
+                                         self.sparse, state, *cores)
+        return out.view(shape + (D,))

@@ -280,6 +280,29 @@ int ttx_bags_compact(int64_t nb, int64_t nnz, const int64_t* indices, const int6
                      int64_t* out_indices, int64_t* out_offsets, int32_t* n_live, void* workspace, size_t workspace_bytes,
                      ttx_stream_t stream);
 
+/* ------------------------------ unpooled rows at padded positions (not in the reference) -----
+ * nn.Embedding(padding_idx=): one row per position, the padding positions zero.  The positions are compacted as n bags of ONE
+ * slot (ttx_bags_compact, offsets == NULL, L = 1), the live ones are planned with the device-side count (ttx_plan_build_n),
+ * contracted (ttx_tt_rows_p) and trained (ttx_tt_backward_rows); these two calls carry rows between the compacted order and
+ * the positions:
+ *
+ *   rank [n + 1]           ttx_bags_compact's out_offsets of that call: rank[i] = live positions in front of i.  Position i is
+ *                          live iff rank[i + 1] > rank[i]; rank[i] is clamped to [0, n - 1] before it addresses anything.
+ *   ttx_rows_expand        out[i, :] = live(i) ? rows[rank[i], :] : 0 for i < n; rows / out [n, D].  Every element of `out` has
+ *                          exactly one writer, no memset runs in front; rows of padding positions are not read.
+ *   ttx_rows_collect       d_rows[rank[i], :] = d_out[i, :] for the live i only; d_out / d_rows [n, D].  Rows of d_rows at and
+ *                          beyond rank[n] are not written (and, a plan's kernels being driven by its live count, not read).
+ *   n == 0                 returns 0 and launches nothing.
+ *   errors                 n < 0, D <= 0, n >= 2^31, a NULL pointer with n > 0, a float pointer not 4-byte aligned (rank not
+ *                          8-byte aligned): -1 with ttx_last_error() set, before anything touches a device.
+ *   kernels                D % 4 == 0 and the float pointers 16-byte aligned: 16-byte loads and stores (rows_expand4_kernel /
+ *                          rows_collect4_kernel), anything else float by float (rows_expand1_kernel / rows_collect1_kernel).
+ *                          Consecutive lanes hold consecutive pieces of the position-ordered array, short rows are grouped into
+ *                          one work-group's tile; element offsets are 64-bit.  No atomics, no LDS, no workspace, nothing read
+ *                          back: bit-identical from run to run, capturable. */
+int ttx_rows_expand(int64_t n, int32_t D, const int64_t* rank, const float* rows, float* out, ttx_stream_t stream);
+int ttx_rows_collect(int64_t n, int32_t D, const int64_t* rank, const float* d_out, float* d_rows, ttx_stream_t stream);
+
 /* ------------------------------ merged bags: per-table batches -> one table-major batch (not in the reference) -----
  * Tables of different cardinality arrive as one (indices, bags[, weights]) batch per table (DLRM's call form); the table-batched
  * lookup takes ONE batch, table-major.  ttx_bags_merge builds it in one launch per TTX_MAX_TABLES_MIXED tables -- concatenate,
