@@ -16,7 +16,7 @@ bench.py): `make_plan` (share the lookup plan between forward and backward; `ded
 the batch share one contraction),
 `profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
 `bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, the unpooled lookup's `rows_expand` /
-`rows_collect`, and `bags_merge` (the per-table
+`rows_collect` (and, with a live cache, `preprocess_indices_async`, `rows_place` / `rows_pick`), and `bags_merge` (the per-table
 batches of a mixed-cardinality group -> one table-major batch, one launch).
 """
 import ctypes as C
@@ -171,6 +171,15 @@ def _load(path):
     L.ttx_rows_expand.argtypes = [i64, i32, vp, vp, vp, vp]
     L.ttx_rows_collect.argtypes = [i64, i32, vp, vp, vp, vp]
     L.ttx_plan_build_n.argtypes = [G, i64, vp, vp, vp, vp, vp, sz, vp]
+    # unpooled rows with a live cache (TTEmbedding(use_cache=True)): the live preprocess with its split point on the device, the
+    # rows between partition order and positions, the cache rows' atomic updates from a device-side split point
+    L.ttx_preprocess_indices_async.argtypes = [i64, vp, i64, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(i32), C.POINTER(i32), vp, vp, vp, vp, sz, vp]
+    L.ttx_rows_place.argtypes = [i64, i64, i64, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.ttx_rows_pick.argtypes = [i64, i64, i64, vp, i32, vp, vp, vp, vp]
+    L.ttx_cache_backward_sgd_n.argtypes = [i64, vp, i32, vp, vp, vp, f32, vp, vp]
+    L.ttx_cache_backward_dense_n.argtypes = [i64, vp, i32, vp, vp, vp, i64, vp, vp]
+    L.ttx_cache_backward_rowwise_adagrad_approx_n.argtypes = [i64, vp, i32, vp, vp, vp, f32, f32, vp, vp, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
@@ -642,6 +651,44 @@ def preprocess_indices_sync(colidx: torch.Tensor, offsets: torch.Tensor, num_tab
     return colidx, rowidx, tableidx, nnz, None
 
 
+def preprocess_indices_async(colidx: torch.Tensor, offsets: torch.Tensor, hashtbl: torch.Tensor, cache_state: torch.Tensor,
+                             update_cache_freq: Optional[torch.Tensor] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Not in the reference: preprocess_indices_sync of ONE table with a live cache, the split point left on the device and no
+    synchronise (ttx_preprocess_indices_async).  -> (pcol, prow, ploc, n_tt_dev): the batch partitioned into misses (in front, in
+    their order) and hits, the bag row of every partitioned lookup, its cache row (-1 for a miss), and the number of misses as
+    one int32 on the device.  `update_cache_freq` folds update_cache_state(colidx, hashtbl, update_cache_freq) into the same
+    launch, in the order "count, then look up"."""
+    dev = _dev(colidx)
+    colidx, offsets = _i64(colidx, "colidx"), _i64(offsets, "offsets")
+    _i64(hashtbl, "hashtbl")
+    nnz, H = colidx.numel(), hashtbl.numel()
+    if H <= 0 or cache_state.dtype != torch.int32 or cache_state.numel() != H:
+        raise RuntimeError("tt_embeddings: need a non-empty hashtbl and cache_state int32[hashtbl_size]")
+    fuse = update_cache_freq is not None
+    if fuse and update_cache_freq.numel() != H:
+        raise RuntimeError("tt_embeddings: hashtbl must match cache_freq")
+    if offsets.numel() < 1 or hashtbl.device != dev or cache_state.device != dev or offsets.device != dev:
+        raise RuntimeError(f"tt_embeddings: offsets (with their closing entry), hashtbl and cache_state must be on {dev}")
+    pcol, prow = torch.empty_like(colidx), torch.empty_like(colidx)
+    ploc = torch.empty(nnz, dtype=torch.int32, device=dev)
+    n_tt_dev = torch.empty(1, dtype=torch.int32, device=dev)
+    if nnz == 0:
+        return pcol, prow, ploc, n_tt_dev.zero_()
+    rowidx, tableidx = torch.empty_like(colidx), torch.empty_like(colidx)
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, lb.ttx_preprocess_workspace_bytes(nnz))
+    num_tt, part = C.c_int32(0), C.c_int32(0)
+    with _guard(dev):
+        _check(lb.ttx_preprocess_indices_async(
+            nnz, colidx.data_ptr(), offsets.numel() - 1, offsets.data_ptr(), 1, 0, H, hashtbl.data_ptr(), cache_state.data_ptr(),
+            rowidx.data_ptr(), tableidx.data_ptr(), pcol.data_ptr(), prow.data_ptr(), ploc.data_ptr(), C.byref(num_tt),
+            C.byref(part), n_tt_dev.data_ptr(), hashtbl.data_ptr() if fuse else None,
+            update_cache_freq.data_ptr() if fuse else None, ws.data_ptr(), ws.numel(), st))
+    return pcol, prow, ploc, n_tt_dev
+
+
 def _check_cached_args(nnz: int, cache_locations: torch.Tensor, rowidx: torch.Tensor) -> None:
     if cache_locations.dtype != torch.int32 or not cache_locations.is_contiguous():
         raise RuntimeError("tt_embeddings: cache_locations must be contiguous int32")
@@ -702,9 +749,20 @@ def _cache_backward_sorted(optim: int, nnz: int, go: torch.Tensor, cache_locatio
                                             ws.data_ptr() if nnz else None, ws.numel(), st))
 
 
+def _skip_ptr(skip_dev: torch.Tensor, dev: torch.device) -> int:
+    if skip_dev.dtype != torch.int32 or skip_dev.numel() != 1 or skip_dev.device != dev:
+        raise RuntimeError(f"tt_embeddings: skip_dev must be one int32 on {dev}, got {skip_dev.dtype} x {skip_dev.numel()} on "
+                           f"{skip_dev.device}")
+    return skip_dev.data_ptr()
+
+
 def cache_backward_sgd(nnz: int, grad_output: torch.Tensor, cache_locations: torch.Tensor, rowidx: torch.Tensor,
-                       learning_rate: float, cache_weight: torch.Tensor, deterministic: Optional[bool] = None) -> None:
-    """tt_embeddings.cpp:105-111."""
+                       learning_rate: float, cache_weight: torch.Tensor, deterministic: Optional[bool] = None,
+                       skip_dev: Optional[torch.Tensor] = None) -> None:
+    """tt_embeddings.cpp:105-111.  `skip_dev` (trailing keyword of the three functions below, not in the reference): one int32 on
+    the device, the number of LEADING entries of cache_locations / rowidx that are not cached -- the arrays are the whole
+    partitioned batch of `nnz` lookups and the update works on [*skip_dev, nnz): no host read-back of the split point
+    (ttx_cache_backward_*_n; `deterministic=None` then looks at nnz, the batch)."""
     if nnz == 0:
         return
     dev = _dev(cache_weight)
@@ -712,14 +770,20 @@ def cache_backward_sgd(nnz: int, grad_output: torch.Tensor, cache_locations: tor
     go = _f32(grad_output, "grad_output")
     _check_cached_args(nnz, cache_locations, rowidx)
     if _use_sorted(deterministic, nnz):
-        return _cache_backward_sorted(OPTIM_SGD, nnz, go, cache_locations, rowidx, learning_rate, 0.0, None, cw)
+        return _cache_backward_sorted(OPTIM_SGD, nnz, go, cache_locations, rowidx, learning_rate, 0.0, None, cw, skip_dev)
+    if skip_dev is not None:
+        with _guard(dev):
+            _check(lib().ttx_cache_backward_sgd_n(nnz, _skip_ptr(skip_dev, dev), cw.size(1), go.data_ptr(), cache_locations.data_ptr(),
+                                                  _i64(rowidx, "rowidx").data_ptr(), learning_rate, cw.data_ptr(), _stream(dev)))
+        return
     with _guard(dev):
         _check(lib().ttx_cache_backward_sgd(nnz, cw.size(1), go.data_ptr(), cache_locations.data_ptr(),
                                             _i64(rowidx, "rowidx").data_ptr(), learning_rate, cw.data_ptr(), _stream(dev)))
 
 
 def cache_backward_dense(nnz: int, grad_output: torch.Tensor, cache_locations: torch.Tensor, rowidx: torch.Tensor,
-                         learning_rate: float, cache_weight: torch.Tensor, deterministic: Optional[bool] = None) -> torch.Tensor:
+                         learning_rate: float, cache_weight: torch.Tensor, deterministic: Optional[bool] = None,
+                         skip_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tt_embeddings.cpp:113-119 (learning_rate unused, as in the reference)."""
     dev = _dev(cache_weight)
     cw = cache_weight.detach()
@@ -727,7 +791,14 @@ def cache_backward_dense(nnz: int, grad_output: torch.Tensor, cache_locations: t
     go = _f32(grad_output, "grad_output")
     _check_cached_args(nnz, cache_locations, rowidx)
     if _use_sorted(deterministic, nnz):
-        _cache_backward_sorted(OPTIM_DENSE, nnz, go, cache_locations, rowidx, 0.0, 0.0, None, out)
+        _cache_backward_sorted(OPTIM_DENSE, nnz, go, cache_locations, rowidx, 0.0, 0.0, None, out, skip_dev)
+        return out
+    if skip_dev is not None:
+        with _guard(dev):
+            _check(lib().ttx_cache_backward_dense_n(nnz, _skip_ptr(skip_dev, dev), cw.size(1), go.data_ptr(),
+                                                    cache_locations.data_ptr() if nnz else None,
+                                                    _i64(rowidx, "rowidx").data_ptr() if nnz else None, cw.size(0),
+                                                    out.data_ptr(), _stream(dev)))
         return out
     with _guard(dev):
         _check(lib().ttx_cache_backward_dense(nnz, cw.size(1), go.data_ptr(),
@@ -740,7 +811,8 @@ def cache_backward_dense(nnz: int, grad_output: torch.Tensor, cache_locations: t
 def cache_backward_rowwise_adagrad_approx(nnz: int, grad_output: torch.Tensor, cache_locations: torch.Tensor,
                                           rowidx: torch.Tensor, learning_rate: float, eps: float,
                                           cache_optimizer_state: torch.Tensor, cache_weight: torch.Tensor,
-                                          deterministic: Optional[bool] = None) -> None:
+                                          deterministic: Optional[bool] = None,
+                                          skip_dev: Optional[torch.Tensor] = None) -> None:
     """tt_embeddings.cpp:121-129."""
     if nnz == 0:
         return
@@ -750,7 +822,14 @@ def cache_backward_rowwise_adagrad_approx(nnz: int, grad_output: torch.Tensor, c
     _dev(cache_optimizer_state)
     _check_cached_args(nnz, cache_locations, rowidx)
     if _use_sorted(deterministic, nnz, adagrad=True):
-        return _cache_backward_sorted(OPTIM_ADAGRAD, nnz, go, cache_locations, rowidx, learning_rate, eps, cache_optimizer_state, cw)
+        return _cache_backward_sorted(OPTIM_ADAGRAD, nnz, go, cache_locations, rowidx, learning_rate, eps, cache_optimizer_state, cw,
+                                      skip_dev)
+    if skip_dev is not None:
+        with _guard(dev):
+            _check(lib().ttx_cache_backward_rowwise_adagrad_approx_n(
+                nnz, _skip_ptr(skip_dev, dev), cw.size(1), go.data_ptr(), cache_locations.data_ptr(), _i64(rowidx, "rowidx").data_ptr(),
+                learning_rate, eps, cache_optimizer_state.data_ptr(), cw.data_ptr(), _stream(dev)))
+        return
     with _guard(dev):
         _check(lib().ttx_cache_backward_rowwise_adagrad_approx(
             nnz, cw.size(1), go.data_ptr(), cache_locations.data_ptr(), _i64(rowidx, "rowidx").data_ptr(),
@@ -928,6 +1007,63 @@ def rows_collect(rank: torch.Tensor, d_out: torch.Tensor) -> torch.Tensor:
     d_rows = torch.empty_like(d_out)
     with _guard(dev):
         _check(lib().ttx_rows_collect(n, d_out.size(1), rank.data_ptr(), d_out.data_ptr(), d_rows.data_ptr(), _stream(dev)))
+    return d_rows
+
+
+# ---- unpooled rows with a live cache (include/ttx.h "unpooled rows with a live cache") ----
+def _split_args(n: int, n_tt, dev: torch.device):
+    """(host n_tt, device pointer or None) of a split point given as an int or as one int32 on the device"""
+    if isinstance(n_tt, torch.Tensor):
+        if n_tt.dtype != torch.int32 or n_tt.numel() != 1 or n_tt.device != dev:
+            raise RuntimeError(f"tt_embeddings: n_tt must be an int or one int32 on {dev}, got {n_tt.dtype} x {n_tt.numel()} on "
+                               f"{n_tt.device}")
+        return n, n_tt.data_ptr()
+    return int(n_tt), None
+
+
+def rows_place(N: int, n_tt, pos: torch.Tensor, loc: torch.Tensor, rows_tt: torch.Tensor, cache_weight: torch.Tensor,
+               rank: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[pos[s], :] = rows_tt[s, :] for the misses s < n_tt, cache_weight[loc[s], :] for the hits n_tt <= s < n = pos.numel(), and
+    exact zeros at the padding positions of `rank` (bags_compact's out_offsets of N one-slot bags; None: no padding, n == N).
+    pos / loc: part_rowidx / part_cache_locations of preprocess_indices_async; n_tt: its split point, one int32 on the device (or
+    an int).  -> out [N, D]; every element is written."""
+    dev = _dev(rows_tt)
+    rows_tt, cw = _f32(rows_tt, "rows_tt"), _f32(cache_weight.detach(), "cache_weight")
+    pos = _i64(pos, "pos")
+    n, D = pos.numel(), cw.size(1)
+    if loc.dtype != torch.int32 or not loc.is_contiguous() or loc.numel() < n:
+        raise RuntimeError("tt_embeddings: loc must be contiguous int32, one entry per partitioned lookup")
+    if rows_tt.dim() != 2 or rows_tt.size(1) != D or rows_tt.size(0) < n or cw.dim() != 2:
+        raise RuntimeError(f"tt_embeddings: rows_tt must be [>= {n}, {D}] beside cache_weight [cache_size, {D}], got {tuple(rows_tt.shape)}")
+    if any(t.device != dev for t in (pos, loc, cw)) or (rank is not None and rank.device != dev):
+        raise RuntimeError(f"tt_embeddings: pos, loc, cache_weight and rank must be on {dev}")
+    if rank is not None:
+        rank = _i64(rank, "rank")
+        if rank.numel() != N + 1:
+            raise RuntimeError(f"tt_embeddings: rank must hold N + 1 = {N + 1} entries, got {rank.numel()}")
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (N, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"tt_embeddings: out must be a contiguous float32 {(N, D)} on {dev}")
+    n_tt_host, n_tt_ptr = _split_args(n, n_tt, dev)
+    with _guard(dev):
+        _check(lib().ttx_rows_place(N, n, n_tt_host, n_tt_ptr, D, pos.data_ptr(), loc.data_ptr(), rows_tt.data_ptr(), cw.data_ptr(),
+                                    cw.size(0), None if rank is None else rank.data_ptr(), out.data_ptr(), _stream(dev)))
+    return out
+
+
+def rows_pick(n_tt, pos: torch.Tensor, d_out: torch.Tensor) -> torch.Tensor:
+    """d_rows[s, :] = d_out[pos[s], :] for the misses s < n_tt: their gradient rows in partition order.  d_out [N, D]
+    -> d_rows [N, D], whose rows at and beyond n_tt are not written (the plan's count keeps the backward away from them)."""
+    dev = _dev(d_out)
+    d_out, pos = _f32(d_out, "d_out"), _i64(pos, "pos")
+    if d_out.dim() != 2 or pos.device != dev or pos.numel() > d_out.size(0):
+        raise RuntimeError(f"tt_embeddings: d_out must be [N, D] on the device of pos with N >= pos.numel(), got {tuple(d_out.shape)}")
+    N, D, n = d_out.size(0), d_out.size(1), pos.numel()
+    d_rows = torch.empty_like(d_out)
+    n_tt_host, n_tt_ptr = _split_args(n, n_tt, dev)
+    with _guard(dev):
+        _check(lib().ttx_rows_pick(N, n, n_tt_host, n_tt_ptr, D, pos.data_ptr(), d_out.data_ptr(), d_rows.data_ptr(), _stream(dev)))
     return d_rows
 
 

@@ -486,6 +486,78 @@ class TTRowsLookupFunction(torch.autograd.Function):
         return tuple(head + list(grads))
 
 
+class TTRowsCachedLookupFunction(torch.autograd.Function):
+    """The unpooled lookup with a LIVE row cache (TTEmbedding(use_cache=True) after cache_populate()).  `indices`
+    holds the n live lookups (all N positions, or -- padding dropped by bags_compact, the live count read back by the module --
+    the first n of the compacted batch) and `offsets` describes them as N one-slot or empty bags (arange(N + 1), or the
+    compaction's `rank`), so the bag row the live preprocess hands back for a partitioned lookup IS its position.  Forward:
+    preprocess_indices_async (frequency update folded in, hits behind the misses, the split point on the device), the plan of the
+    misses (make_plan(n_dev=split point), no bag rows), their contraction into scratch rows, and rows_place -- the misses' rows and
+    the hits' cache rows to their positions, zeros at the padding.  Backward: rows_pick (the misses' gradient rows in partition
+    order), the per-lookup backward / fused optimizer on the plan, and the cache rows' update from the gradient [N, D] itself
+    with rowidx = the positions and skip_dev = the split point: SGD, row-wise Adagrad, or the dense gradient of cache_weight
+    (returned in its slot).  `parts` = k > 1: the geometry handed in is the core-0 row split's; the partitioned indices are
+    expanded to their k part lookups (split0_expand over `unit_offsets`, n one-lookup bags: the first k n_tt of them are the
+    misses', a plan count computed on the device), and the rows [n, D] ARE the parts' [k n, D / k].
+    Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, N: int, D: int, parts: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
+                indices: torch.Tensor, offsets: torch.Tensor, rank: Optional[torch.Tensor], unit_offsets: Optional[torch.Tensor],
+                hashtbl: torch.Tensor, cache_state: torch.Tensor, cache_freq: Optional[torch.Tensor], det: Optional[bool],
+                optimizer: OptimType,
+                learning_rate: float, eps: float, sparse: bool, cache_optimizer_state: Optional[torch.Tensor],
+                cache_weight: torch.Tensor, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
+        k = max(1, parts)
+        n = indices.numel()
+        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
+        ctx.N, ctx.n, ctx.D, ctx.k, ctx.det = N, n, D, k, det
+        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
+        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        pcol, prow, ploc, n_tt = _engine.preprocess_indices_async(indices, offsets, hashtbl, cache_state, cache_freq)
+        lookups, n_dev = pcol, n_tt
+        if k > 1:
+            # (unit_offsets: n one-lookup bags -- part lookups k s .. k s + k - 1 belong to partition slot s, so the misses' parts lead)
+            lookups, _ = _engine.split0_expand(pcol, unit_offsets, k, tt_p_shapes[1] * tt_p_shapes[2])
+            n_dev = n_tt * k
+        tableidx = torch.zeros_like(lookups)  # (one table)
+        plan = _engine.make_plan(1, tt_p_shapes, tt_q_shapes, tt_ranks, k * n, lookups, tableidx, n_dev=n_dev)  # (no bag rows)
+        rows = _engine.tt_rows_p(1, D // k, tt_p_shapes, tt_q_shapes, tt_ranks, lookups, tableidx, list(tt_cores), plan)
+        ctx.plan = plan
+        ctx.save_for_backward(lookups, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight)
+        return _engine.rows_place(N, n_tt, prow, ploc, rows.view(n, D), cache_weight, rank)
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        lookups, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight = ctx.saved_tensors
+        p, q, ranks = ctx.geometry
+        N, n, D, k = ctx.N, ctx.n, ctx.D, ctx.k
+        cores = list(ctx.tt_cores)
+        head: List[Optional[torch.Tensor]] = [None] * 21
+        d_out = d_output.contiguous().view(N, D)
+        d_rows = _engine.rows_pick(n_tt, prow, d_out)[:n].view(k * n, D // k)
+        det = ctx.det
+        auto = getattr(_engine, "_use_sorted", None)
+        if det is None and auto is not None:  # "auto" looks at the BATCH (misses + hits), as TTLookupFunction.backward does
+            det = auto(None, n, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
+        if ctx.sparse:
+            if ctx.optimizer in _SGD_LIKE:
+                _engine.tt_backward_rows(_engine.OPTIM_SGD, D // k, ctx.learning_rate, 0.0, p, q, ranks, k * n, lookups, tableidx,
+                                         d_rows, cores, None, ctx.plan)
+                _engine.cache_backward_sgd(n, d_out, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det, skip_dev=n_tt)
+            else:
+                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, D // k, ctx.learning_rate, ctx.eps, p, q, ranks, k * n, lookups,
+                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
+                _engine.cache_backward_rowwise_adagrad_approx(n, d_out, ploc, prow, ctx.learning_rate, ctx.eps,
+                                                              cache_optimizer_state, cache_weight, deterministic=det, skip_dev=n_tt)
+            return tuple(head + [None] * len(cores))
+        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, D // k, 0.0, 0.0, p, q, ranks, k * n, lookups, tableidx, d_rows,
+                                         cores, None, ctx.plan)
+        head[19] = _engine.cache_backward_dense(n, d_out, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det,
+                                                skip_dev=n_tt)
+        return tuple(head + list(grads))
+
+
 class _RowsAtPositionsFunction(torch.autograd.Function):
     """rows_expand / rows_collect around a lookup that returned the rows of the live positions only (TTEmbedding's dedup route
     with padding_idx, where the live count n has been read back): rows [n, D] -> out [N, D], zeros at the padding."""
@@ -1440,7 +1512,7 @@ class TTEmbedding(TTEmbeddingBag):
     the device in front of the lookup and put back behind it; a TT table holds no independent padding row, see
     TTEmbeddingBag).  Gradients as in the bag modules: `sparse=True` applies the fused SGD / Adagrad inside backward,
     `sparse=False` leaves dense gradients on `tt_cores[t].grad`.  Parameters, buffers and state_dict() are those of
-    `TTEmbeddingBag(use_cache=False)` of the same geometry: a checkpoint loads in either direction.
+    `TTEmbeddingBag(use_cache=False)` of the same geometry (the default; see `use_cache` below): a checkpoint loads in either direction.
 
     Routes, all without a host synchronisation unless noted: plain -- a plan without bag rows, the contraction
     straight into the output buffer, the per-lookup backward; padding_idx -- bags_compact over one-slot bags, the plan of the
@@ -1448,16 +1520,31 @@ class TTEmbedding(TTEmbeddingBag):
     a rows buffer [N, D] being the parts' [k N, D / k]; dedup=True -- the bag module's duplicate-sharing sequence with one bag per
     position (with padding_idx the live count is read back: not capturable); CPU tensors -- the bag module's reference-shaped
     route, one bag per live position (what the tests' oracle engine runs).
-    No cache, no table batching, no prefetch, no C++ node, no max_norm / scale_grad_by_freq."""
+
+    `use_cache=True` (with `cache_size`, `hashtbl_size`, `reference_exact_populate`, `deterministic_cache_update` as in
+    TTEmbeddingBag, whose parameters, buffers and state_dict() the module then has): the LFU row cache under the unpooled call
+    form.  While the cache warms up the routes above run, the batch's live indices counted first (`dedup` applies here only);
+    after cache_populate() TTRowsCachedLookupFunction takes over -- the live preprocess with its split point on the device over N
+    one-slot bags (so a partitioned lookup's bag row IS its position), the plan and contraction of the misses, rows_place (the
+    misses' rows and the hits' cache rows to their positions, zeros at the padding), and backward rows_pick, the per-lookup
+    backward and the cache rows' update (SGD, row-wise Adagrad, or the dense gradient of cache_weight) from the split point on.
+    Nothing is read back without padding_idx: the step is capturable and the hit / miss split is not baked into the graph; with
+    padding_idx the live count is read back (RuntimeError under capture).  q0 > 4 with an exact split: the misses take the part
+    lookups, cached rows are whole rows.
+    No table batching, no prefetch, no C++ node, no max_norm / scale_grad_by_freq."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, tt_ranks: List[int],
                  tt_p_shapes: Optional[List[int]] = None, tt_q_shapes: Optional[List[int]] = None,
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 device: Optional[torch.device] = None, padding_idx: Optional[int] = None, dedup: bool = False) -> None:
+                 device: Optional[torch.device] = None, padding_idx: Optional[int] = None, dedup: bool = False,
+                 use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0, reference_exact_populate: bool = False,
+                 deterministic_cache_update: Optional[bool] = None) -> None:
         super().__init__(num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer, learning_rate, eps,
-                         sparse, use_cache=False, weight_dist=weight_dist, enforce_embedding_dim=enforce_embedding_dim,
-                         device=device, include_last_offset=True, dedup=bool(dedup), mode="sum", padding_idx=padding_idx)
+                         sparse, use_cache=bool(use_cache), cache_size=cache_size, hashtbl_size=hashtbl_size, weight_dist=weight_dist,
+                         enforce_embedding_dim=enforce_embedding_dim, device=device, include_last_offset=True, dedup=bool(dedup),
+                         reference_exact_populate=reference_exact_populate, deterministic_cache_update=deterministic_cache_update,
+                         mode="sum", padding_idx=padding_idx)
 
     def prefetch(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> bool:
         return False  # (no prologue to plan ahead: there are no bags)
@@ -1469,6 +1556,46 @@ class TTEmbedding(TTEmbeddingBag):
         """the bag module's sum route with one bag per lookup -> [n, D] (CPU tensors, duplicate sharing)"""
         n = live.numel()
         return self._forward_sum(live, self._fixed_offsets(live.device, n, 1), closed=True).view(n, self.embedding_dim)
+
+    def _split_geometry(self, use_state: bool):
+        """-> (k, p, q, cores, state): the geometry a rows lookup runs on.  q0 = k q0' with an exact split: k part lookups per
+        position in the table [k p0, p1, p2] x [q0', q1, q2] (views of core 0 and its optimizer state: the same memory); k = 1
+        otherwise (the module's own geometry)."""
+        k = self.__dict__.get("_split0", 0) if not self.__dict__.get("_pad0", 0) else 0
+        k = k if k > 1 else 1
+        p, q = self.tt_p_shapes, self.tt_q_shapes
+        cores, state = list(self.tt_cores), list(self.optimizer_state) if use_state else []
+        if k > 1:
+            c0 = cores[0]
+            cores[0] = c0.view(1, k * p[0], c0.size(2) // k)
+            if use_state:
+                state[0] = state[0].view(1, k * p[0], state[0].size(2) // k)
+            p, q = [k * p[0], p[1], p[2]], [q[0] // k, q[1], q[2]]
+        return k, p, q, cores, state
+
+    def _forward_cached(self, flat: torch.Tensor, N: int, pad: Optional[int], use_state: bool) -> torch.Tensor:
+        """GPU tensors, the cache live -> [N, D] (TTRowsCachedLookupFunction).  Without padding_idx nothing is read back; with it
+        the live count is (it sizes the partition), as in the bag module."""
+        D, dev = self.embedding_dim, flat.device
+        rank, n = None, N
+        if pad is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TTEmbedding(use_cache=True, padding_idx=): with a live cache the live count is read back to the "
+                                   "host to size the hit / miss partition -- not capturable in a hipGraph on this route")
+            flat, rank, n_live = _engine.bags_compact(flat, None, 1, pad)
+            n = int(n_live.item())
+            if n == 0:  # padding only: zeros, nothing trained, nothing counted (zero dense gradients, as an empty batch gives)
+                out = TTRowsLookupFunction.apply(0, D, 1, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat[:0], None, None,
+                                                 self.optimizer, self.learning_rate, self.eps, self.sparse,
+                                                 list(self.optimizer_state), *self.tt_cores)
+                return torch.zeros((N, D), dtype=torch.float32, device=dev) + out.sum()
+            flat = flat[:n]
+        k, p, q, cores, state = self._split_geometry(use_state)
+        unit = self._fixed_offsets(dev, n, 1)
+        return TTRowsCachedLookupFunction.apply(
+            N, D, k, p, q, self.tt_ranks, flat, unit if rank is None else rank, rank, unit if k > 1 else None, self.hashtbl,
+            self.cache_state, self.cache_freq, self.__dict__.get("deterministic_cache_update"), self.optimizer, self.learning_rate,
+            self.eps, self.sparse, self.cache_optimizer_state if use_state else None, self.cache_weight, state, *cores)
 
     def forward(self, indices: torch.Tensor) -> torch.Tensor:  # noqa: D102 -- see the class
         if indices.dtype not in (torch.int64, torch.int32):
@@ -1497,9 +1624,12 @@ class TTEmbedding(TTEmbeddingBag):
             else:
                 out = out.index_put((keep,), self._bag_rows(flat[keep].contiguous()))
             return out.view(shape + (D,))
+        if self.use_cache and not self.warmup:
+            return self._forward_cached(flat, N, pad, use_state).view(shape + (D,))
         if self.dedup:
             # duplicate positions share one contraction: the bag module's sequence (make_plan(dedup=True), ttx_tt_forward_dd /
             # _backward_dd) with B = N bags of one lookup; a batch ttx_dedup_bytes refuses takes the plain plan there
+            # (while a cache warms up that sequence counts the batch's live indices itself)
             if pad is None:
                 return self._bag_rows(flat).view(shape + (D,))
             if torch.cuda.is_current_stream_capturing():
@@ -1512,24 +1642,26 @@ class TTEmbedding(TTEmbeddingBag):
                                                  self.eps, self.sparse, list(self.optimizer_state), *self.tt_cores)
                 return (torch.zeros((N, D), dtype=torch.float32, device=flat.device) + out.sum()).view(shape + (D,))
             return _RowsAtPositionsFunction.apply(self._bag_rows(live[:n].contiguous()), rank).view(shape + (D,))
-        k = self.__dict__.get("_split0", 0) if not self.__dict__.get("_pad0", 0) else 0
-        k = k if k > 1 else 1
         rank = n_dev = None
         if pad is not None:
             flat, rank, n_dev = _engine.bags_compact(flat, None, 1, pad)
-        cores, state = list(self.tt_cores), list(self.optimizer_state) if use_state else []
+        if self.use_cache:
+            # the cache warms up: the existing routes, the batch's LIVE indices counted first (with padding_idx the live count
+            # is read back for that, as the bag module does for a cache beside padding)
+            if pad is None:
+                self.update_cache(flat)
+            else:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("TTEmbedding(use_cache=True, padding_idx=): the live count is read back to the host to count "
+                                       "the live indices -- not capturable in a hipGraph on this route")
+                self.update_cache(flat[:int(n_dev.item())])
+        k, p, q, cores, state = self._split_geometry(use_state)
         if k > 1:
-            # q0 = k q0': k part lookups per position in the table [k p0, p1, p2] x [q0', q1, q2] (views of core 0 and its
-            # optimizer state: the same memory) -- position n's parts are lookups k n .. k n + k - 1, their rows of D / k columns
-            # ARE row n of [N, D]; of a compacted batch the first k n_live part lookups are the live ones
+            # position n's parts are lookups k n .. k n + k - 1, their rows of D / k columns ARE row n of [N, D]; of a compacted
+            # batch the first k n_live part lookups are the live ones
             flat, _ = _engine.split0_expand(flat, self._fixed_offsets(flat.device, N, 1), k, p[1] * p[2])
             if n_dev is not None:
                 n_dev = n_dev * k
-            c0 = cores[0]
-            cores[0] = c0.view(1, k * p[0], c0.size(2) // k)
-            if use_state:
-                state[0] = state[0].view(1, k * p[0], state[0].size(2) // k)
-            p, q = [k * p[0], p[1], p[2]], [q[0] // k, q[1], q[2]]
         out = TTRowsLookupFunction.apply(N, D, k, p, q, ranks, flat, rank, n_dev, self.optimizer, self.learning_rate, self.eps,
                                          self.sparse, state, *cores)
         return out.view(shape + (D,))

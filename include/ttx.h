@@ -303,6 +303,45 @@ int ttx_bags_compact(int64_t nb, int64_t nnz, const int64_t* indices, const int6
 int ttx_rows_expand(int64_t n, int32_t D, const int64_t* rank, const float* rows, float* out, ttx_stream_t stream);
 int ttx_rows_collect(int64_t n, int32_t D, const int64_t* rank, const float* d_out, float* d_rows, ttx_stream_t stream);
 
+/* ------------------------------ unpooled rows with a live cache (not in the reference) -----
+ * nn.Embedding on a table whose row cache is live: the N positions (padding dropped first: ttx_bags_compact over one-slot bags)
+ * go through the live preprocess (ttx_preprocess_indices_async with offsets = N one-slot bags, or = rank with padding), which
+ * leaves the n live lookups in PARTITION order -- the misses, in their order, in [0, n_tt), the hits in [n_tt, n) -- with the
+ * split point on the device.  The misses are planned (ttx_plan_build_n), contracted (ttx_tt_rows_p) and trained
+ * (ttx_tt_backward_rows); the hits' rows are trained in place (ttx_cache_backward_*_n / ttx_cache_backward_sorted with
+ * rowidx = pos, skip_dev = n_tt_dev, on the gradient [N, D] itself).  These two calls carry rows between partition order and the
+ * positions:
+ *
+ *   pos [n]                part_rowidx of that preprocess: the position of partition slot s; clamped to [0, N - 1] before it
+ *                          addresses anything.  Injective onto the live positions.
+ *   loc [n]                part_cache_locations: slot s's cache row for s >= n_tt (-1 in front of it, where it is not read);
+ *                          clamped to [0, cache_size - 1] before it addresses anything.
+ *   n_tt, n_tt_dev         the split point: *n_tt_dev (a device int32, clamped to [0, n]) -- or, n_tt_dev == NULL, the host's n_tt:
+ *                          NULL gives the plain entry point.  n_tt <= n is checked either way (pass n with a device count).
+ *   rank                   NULL: no padding, n == N.  Else ttx_bags_compact's out_offsets [N + 1] as for ttx_rows_expand:
+ *                          position i is padding iff not rank[i + 1] > rank[i].
+ *   ttx_rows_place         out[pos[s], :] = s < n_tt ? rows_tt[s, :] : cache_weight[loc[s], :] for s < n, and out[i, :] = 0 for
+ *                          every padding position i < N; rows_tt [>= n_tt, D] (read for s < n_tt only), cache_weight
+ *                          [cache_size, D], out [N, D].  The gather of the cache rows is part of the launch: there is no rows
+ *                          buffer for the hits.  Every element of `out` has exactly one writer, no memset runs in front.
+ *   ttx_rows_pick          d_rows[s, :] = d_out[pos[s], :] for s < n_tt only; d_out [N, D], d_rows [>= n_tt, D].  Rows of d_rows at
+ *                          and beyond n_tt are not written (and, a plan's kernels being driven by its count, not read).
+ *   N == 0 or n == 0       returns 0; with N > 0, n == 0 and a rank ttx_rows_place still zeroes the (padding) rows.
+ *   errors                 a negative size, D <= 0, N >= 2^31, n > N, n_tt > n, rank == NULL with n != N, cache_size <= 0 while
+ *                          n_tt < n with a host count, a NULL pointer that would be dereferenced (with a device count: any of them),
+ *                          a float / int32 pointer not 4-byte aligned, pos / rank not 8-byte aligned: -1 with ttx_last_error()
+ *                          set, before anything touches a device.
+ *   kernels                D % 4 == 0 and the float pointers 16-byte aligned: 16-byte loads and stores (rc_place4_kernel /
+ *                          rc_pick4_kernel), anything else float by float (rc_place1_kernel / rc_pick1_kernel).  Consecutive lanes
+ *                          hold consecutive pieces of a row, short rows are grouped into one work-group's tile, the grid is capped
+ *                          and strides over the tiles; element offsets are 64-bit.  One launch each.  No atomics, no LDS, no
+ *                          workspace, nothing read back: bit-identical from run to run, capturable. */
+int ttx_rows_place(int64_t N, int64_t n, int64_t n_tt, const int32_t* n_tt_dev, int32_t D, const int64_t* pos, const int32_t* loc,
+                   const float* rows_tt, const float* cache_weight, int64_t cache_size, const int64_t* rank, float* out,
+                   ttx_stream_t stream);
+int ttx_rows_pick(int64_t N, int64_t n, int64_t n_tt, const int32_t* n_tt_dev, int32_t D, const int64_t* pos, const float* d_out,
+                  float* d_rows, ttx_stream_t stream);
+
 /* ------------------------------ merged bags: per-table batches -> one table-major batch (not in the reference) -----
  * Tables of different cardinality arrive as one (indices, bags[, weights]) batch per table (DLRM's call form); the table-batched
  * lookup takes ONE batch, table-major.  ttx_bags_merge builds it in one launch per TTX_MAX_TABLES_MIXED tables -- concatenate,

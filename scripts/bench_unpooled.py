@@ -19,7 +19,17 @@ Times are device events around a window of `--steps` steps; both variants are wa
     python scripts/bench_unpooled.py [--steps 200] [--repeats 5] [--workloads cfg2-10k,token-4k] [--json FILE] [--md FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_unpooled.py --trace      # kernel times, a run of its own
 
-One JSON line per (workload, padding, variant) on stdout; --md writes the table."""
+One JSON line per (workload, padding, variant) on stdout; --md writes the table.
+
+--cache: the same comparison with a LIVE row cache (DESIGN.md 4.12 "with the row cache"), no padding, a Zipf(1.2) index stream:
+
+  embedding   TTEmbedding(use_cache=True): partition, plan of the misses, contraction, rows_place / rows_pick, cache rows' update
+  bags        TTEmbeddingBag(use_cache=True)(indices, arange(N + 1)): one bag per position through the cache-live C++ node
+
+on the token-like table and on cfg2's table at 4,096 and 32,768 positions (CACHE_WORKLOADS).  Both modules count the same
+warm-up batches of the stream and populate before anything is timed; the hit share of the timed batches is reported.
+
+    python scripts/bench_unpooled.py --cache [--steps 200] [--repeats 5] [--workloads token-4k,cfg2-32k] [--json FILE] [--md FILE]"""
 import argparse
 import json
 import os
@@ -43,6 +53,14 @@ WORKLOADS = {
     "token-4k": (50257, 512, None, [8, 8, 8], [32, 32], (8, 512)),
     "token-32k": (50257, 512, None, [8, 8, 8], [32, 32], (64, 512)),
 }
+# --cache: name -> (num_embeddings, D, p, q, ranks, index shape, cache rows, hash table slots)
+CACHE_WORKLOADS = {
+    "token-4k": (50257, 512, None, [8, 8, 8], [32, 32], (8, 512), 4096, 1 << 17),
+    "token-32k": (50257, 512, None, [8, 8, 8], [32, 32], (64, 512), 4096, 1 << 17),
+    "cfg2-4k": (200 * 220 * 250, 64, [200, 220, 250], [4, 4, 4], [32, 32], (8, 512), 16384, 1 << 20),
+    "cfg2-32k": (200 * 220 * 250, 64, [200, 220, 250], [4, 4, 4], [32, 32], (64, 512), 16384, 1 << 20),
+}
+ZIPF_ALPHA = 1.2
 ITERS = 4
 VARIANTS = ("embedding", "bags")
 SHARES = (0.0, 0.3)
@@ -132,6 +150,70 @@ def measure(wl, share, steps, warmup, repeats):
     return recs
 
 
+def zipf_requests(seed, shape, E_, count):
+    """`count` batches of a Zipf(ZIPF_ALPHA) stream over E_ keys (the ranks scattered over the key space by a fixed multiplier)"""
+    rs = np.random.RandomState(seed)
+    return [(((rs.zipf(ZIPF_ALPHA, size=shape).astype(np.int64) - 1) % E_) * 2654435761 % E_).astype(np.int64) for _ in range(count)]
+
+
+def measure_cache(wl, steps, warmup, repeats):
+    E_, D, p, q, r, shape, cache_size, hashtbl_size = CACHE_WORKLOADS[wl]
+    N = int(np.prod(shape))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = zipf_requests(1236, shape, E_, 16 + ITERS)
+    warm, reqs = [torch.from_numpy(a).to(dev) for a in stream[:16]], [torch.from_numpy(a).to(dev) for a in stream[16:]]
+    grad = (torch.rand(shape + (D,), device=dev) * 0.1).contiguous()
+    off = torch.arange(N + 1, device=dev)
+    kw = dict(optimizer=ops.OptimType.SGD, learning_rate=1e-6, sparse=True, weight_dist="uniform", device=dev, use_cache=True,
+              cache_size=cache_size, hashtbl_size=hashtbl_size)
+    torch.manual_seed(1234)
+    mods = {"embedding": ops.TTEmbedding(E_, D, r, p, q, **kw), "bags": ops.TTEmbeddingBag(E_, D, r, p, q, **kw)}
+    with torch.no_grad():
+        for dst, src in zip(mods["bags"].tt_cores, mods["embedding"].tt_cores):
+            dst.copy_(src)
+
+    def step(variant, idx, g):
+        m = mods[variant]
+        out = m(idx) if variant == "embedding" else m(idx.reshape(-1), off)
+        out.backward(g.view(out.shape))
+
+    with torch.no_grad():
+        for v in VARIANTS:
+            for b in warm:
+                step_out = mods[v](b) if v == "embedding" else mods[v](b.reshape(-1), off)
+                del step_out
+            mods[v].cache_populate()
+    m = mods["embedding"]
+    keys = m.hashtbl[m.cache_state >= 0].cpu().numpy()
+    hit_share = float(np.mean([np.isin(a, keys).mean() for a in stream[16:]]))
+    eager = {v: [] for v in VARIANTS}
+    replayed = {v: [] for v in VARIANTS}
+    for v in VARIANTS:
+        for k in range(warmup):
+            step(v, reqs[k % ITERS], grad)
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for v in VARIANTS:
+            eager[v].append(window(lambda k, v=v: step(v, reqs[k % ITERS], grad), steps))
+    graphs = {v: ttx_graph.GraphedStep(lambda i, g, v=v: step(v, i, g), (reqs[0], grad), warmup=2) for v in VARIANTS}
+    for v in VARIANTS:
+        graphs[v](reqs[0], grad)
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for v in VARIANTS:
+            replayed[v].append(window(lambda k, v=v: graphs[v](reqs[k % ITERS], grad), steps))
+    recs = []
+    for v in VARIANTS:
+        e, rp = np.asarray(eager[v]), np.asarray(replayed[v])
+        recs.append({"workload": wl, "cache": True, "positions": N, "D": D, "padding": 0.0, "hit_share": round(hit_share, 3),
+                     "variant": v, "split0": int(getattr(mods[v], "_split0", 0)),
+                     "eager_ms": round(float(np.median(e)), 4), "eager_spread_ms": round(float(e.max() - e.min()), 4),
+                     "replayed_ms": round(float(np.median(rp)), 4), "replayed_spread_ms": round(float(rp.max() - rp.min()), 4),
+                     "steps": steps, "repeats": repeats})
+    del graphs
+    return recs
+
+
 def trace_run(workloads, steps=50):
     """--trace: only TTEmbedding with 30 % padding, eager, `steps` steps per workload -- what to put behind
     `rocprofv3 --kernel-trace --stats --` for the kernel times of rows_expand* / rows_collect*"""
@@ -147,10 +229,13 @@ def trace_run(workloads, steps=50):
 
 
 def markdown(recs):
-    lines = ["| workload | positions | D | padding | variant | eager ms/step (spread) | replayed ms/step (spread) |", "|---|---|---|---|---|---|---|"]
+    cache = any(r.get("cache") for r in recs)
+    third = "hit share" if cache else "padding"
+    lines = [f"| workload | positions | D | {third} | variant | eager ms/step (spread) | replayed ms/step (spread) |", "|---|---|---|---|---|---|---|"]
     for r in recs:
         rep = "not capturable" if r["replayed_ms"] is None else f"{r['replayed_ms']:.4f} ({r['replayed_spread_ms']:.4f})"
-        lines.append(f"| {r['workload']} | {r['positions']} | {r['D']} | {r['padding']:.0%} | {r['variant']} | {r['eager_ms']:.4f} ({r['eager_spread_ms']:.4f}) "
+        share = r["hit_share"] if cache else r["padding"]
+        lines.append(f"| {r['workload']} | {r['positions']} | {r['D']} | {share:.0%} | {r['variant']} | {r['eager_ms']:.4f} ({r['eager_spread_ms']:.4f}) "
                      f"| {rep} |")
     return "\n".join(lines) + "\n"
 
@@ -160,19 +245,22 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--workloads", default=",".join(WORKLOADS))
+    ap.add_argument("--workloads", default=None, help="comma-separated; default: all of WORKLOADS (--cache: of CACHE_WORKLOADS)")
+    ap.add_argument("--cache", action="store_true", help="the cache-live comparison on a Zipf stream (CACHE_WORKLOADS)")
     ap.add_argument("--json", default=None, help="also append the lines to this file")
     ap.add_argument("--md", default=None, help="write the table to this file")
     ap.add_argument("--trace", action="store_true", help="run only TTEmbedding with padding, eager (for a kernel trace)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    workloads = (args.workloads or ",".join(CACHE_WORKLOADS if args.cache else WORKLOADS)).split(",")
     if args.trace:
-        trace_run(args.workloads.split(","))
+        trace_run(workloads)
         return
     allrecs = []
-    for wl in args.workloads.split(","):
-        for share in SHARES:
-            for rec in measure(wl, share, args.steps, args.warmup, args.repeats):
+    for wl in workloads:
+        for share in ((None,) if args.cache else SHARES):
+            for rec in (measure_cache(wl, args.steps, args.warmup, args.repeats) if args.cache
+                        else measure(wl, share, args.steps, args.warmup, args.repeats)):
                 allrecs.append(rec)
                 line = json.dumps(rec)
                 print(line, flush=True)
