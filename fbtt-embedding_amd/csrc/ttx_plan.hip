@@ -38,6 +38,14 @@ namespace ttx {
 constexpr int kPlanThreads = 1024;
 constexpr int kPlanWaves = kPlanThreads / kWave;
 
+// which way the last plan was built (ttx_debug_plan_route, include/ttx_test_hooks.h): the test build only
+#ifdef TTX_TEST_HOOKS
+static int g_plan_route = 0;
+#define TTX_PLAN_ROUTE(id) (g_plan_route = (id))
+#else
+#define TTX_PLAN_ROUTE(id) ((void)0)
+#endif
+
 int max_chunks(const Dims& d, long long nnz, int MC) {
   if (MC <= 0) MC = 1;  // (a shape no kernel variant fits: the sizes stay defined, the launch reports TTX_EUNSUPPORTED)
   long long a = nnz < d.S[1] ? nnz : d.S[1];
@@ -177,7 +185,7 @@ __device__ __forceinline__ unsigned clamp_idx32(long long idx) {
   return idx < 0 ? 0u : (idx > 0xffffffffll ? 0xffffffffu : (unsigned)idx);
 }
 
-// ---- tiny-batch path (nnz <= 1024; the template extents still allow 16384): everything between the index load and
+// ---- tiny-batch path (nnz <= 1024: one batch of 64 per wave, the only instantiation is kBPW = 2): everything between the index load and
 // the final stores stays on chip.  Each thread keeps its (key, value, rank) triples in
 // registers (wave w owns the contiguous range [w*per, (w+1)*per) of the current
 // order, 64 per batch), passes exchange through LDS, and the pivot work-group emits the
@@ -1301,6 +1309,7 @@ __global__ __launch_bounds__(kWideThreads) void mbp_scatter_kernel(
 template <int BITS, bool GRP>
 static int plan_build_wide(const Dims& d, int N, const int* n_dev, const int64_t* indices, const int64_t* tableidx,
                            const int64_t* rowidx, const Plan& P, hipStream_t stream, const GrpArgs& ga) {
+  TTX_PLAN_ROUTE((GRP ? TTX_ROUTE_GROUPED : TTX_ROUTE_WIDE) + BITS);
   constexpr size_t lds = BITS >= 12 ? (size_t)kWideWaves * (1 << BITS) * sizeof(unsigned short) + (size_t)(kWideWaves + (1 << BITS)) * sizeof(int)
                                     : (size_t)(kWideWaves * (1 << BITS) + kWideWaves) * sizeof(int);
   if (lds > 64 * 1024) {
@@ -1439,6 +1448,7 @@ static int plan_build_mb(const Dims& d, int N, const int* n_dev, const int64_t* 
     }
   }
   if (maxp == 1 && N <= kOneMaxN && !d.tab) {
+    TTX_PLAN_ROUTE(TTX_ROUTE_SINGLE);
     hipLaunchKernelGGL(mb_single_kernel<false>, dim3((N + kOneWaves * kOneUnit - 1) / (kOneWaves * kOneUnit) + TTX_PLAN_XWG, d.T),
                        dim3(kOneThreads), 0, stream, d, N, n_dev, indices, tableidx, rowidx, P, Prologue{}, ProBatch{});
     TTX_HIP(hipGetLastError());
@@ -1475,6 +1485,7 @@ static int plan_build_mb(const Dims& d, int N, const int* n_dev, const int64_t* 
     }
   }
   if (maxp > 1 || N > kMbFuseU * 4096 || d.tab) {  // 8-bit passes on full work-groups, then mb_finish
+    TTX_PLAN_ROUTE(TTX_ROUTE_MULTIPASS + maxp);
     MbpArgs B;
     B.N = N;
     B.n_dev = n_dev;
@@ -1494,6 +1505,7 @@ static int plan_build_mb(const Dims& d, int N, const int* n_dev, const int64_t* 
   }
   // one 8-bit pass, up to ~1 M lookups: wave units of 256..4096 positions (<= kMbFuseU of them), the
   // scatter launch scans the unit counts itself and its first work-group writes offsets / chunk list
+  TTX_PLAN_ROUTE(TTX_ROUTE_UNITS);
   A.unit = 256;
   if ((N + 255) / 256 > kMbFuseU) A.unit = ((N + kMbFuseU - 1) / kMbFuseU + 63) / 64 * 64;
   A.U = (N + A.unit - 1) / A.unit;
@@ -1570,23 +1582,15 @@ int plan_build(const Dims& d, long long nnz, const int64_t* indices,
   ProfScope ps(TTX_PROF_PLAN, stream);
   if (nnz > 1024 || !d.idx32 || n_dev)
     return plan_build_mb(d, (int)nnz, n_dev, indices, tableidx, rowidx, P, stream, offsets, bags_per_table);
-  {  // tiny batch: one launch, one work-group per core, everything on chip
+  {  // tiny batch: one launch, one work-group per core, everything on chip.  16 waves over <= 1024 lookups: every wave holds at
+    // most ONE batch of 64 (per = 64, nb <= 1), so one instantiation serves the route (kBPW = 2, the extent it has always run with)
     const size_t lds = (256 * kPlanWaves + 32 + 2 * ((nnz + 63) / 64 * 64)) * sizeof(int);
-    const int per = (((int)nnz + kPlanWaves - 1) / kPlanWaves + kWave - 1) / kWave * kWave;
-    const int nb = per / kWave;
-#define TTX_PLAN_LAUNCH(BPW)                                                                          \
-  do {                                                                                                \
-    const int rc_attr = allow_dynamic_lds((const void*)plan_small_kernel<BPW>, 160 * 1024);          \
-    if (rc_attr) return rc_attr;                                                                      \
-    hipLaunchKernelGGL(plan_small_kernel<BPW>, dim3(d.T), dim3(kPlanThreads), lds, stream, d,         \
-                       (int)nnz, indices, tableidx, rowidx, P, debug_stamps());                               \
-  } while (0)
-    if (nb <= 2) TTX_PLAN_LAUNCH(2);
-    else if (nb <= 4) TTX_PLAN_LAUNCH(4);
-    else if (nb <= 8) TTX_PLAN_LAUNCH(8);
-    else if (nb <= 12) TTX_PLAN_LAUNCH(12);
-    else TTX_PLAN_LAUNCH(16);
-#undef TTX_PLAN_LAUNCH
+    static_assert(1024 <= kPlanWaves * kWave, "the tiny plan holds one batch of 64 lookups per wave");
+    TTX_PLAN_ROUTE(TTX_ROUTE_TINY);
+    const int rc_attr = allow_dynamic_lds((const void*)plan_small_kernel<2>, 160 * 1024);
+    if (rc_attr) return rc_attr;
+    hipLaunchKernelGGL(plan_small_kernel<2>, dim3(d.T), dim3(kPlanThreads), lds, stream, d, (int)nnz, indices, tableidx, rowidx, P,
+                       debug_stamps());
   }
   TTX_HIP(hipGetLastError());
   return TTX_OK;
@@ -1615,6 +1619,7 @@ int plan_build_batches(const Dims& d, int nbatch, long long nnz, const int* n_de
   mb.out_stride = nnz;
   mb.plan_stride = (long long)plan_stride;
   const int N = (int)nnz;
+  TTX_PLAN_ROUTE(TTX_ROUTE_MULTIBATCH);
   hipLaunchKernelGGL(mb_single_kernel<false>,
                      dim3((N + kOneWaves * kOneUnit - 1) / (kOneWaves * kOneUnit) + TTX_PLAN_XWG, d.T, nbatch),
                      dim3(kOneThreads), 0, stream, d, N, n_dev, indices, tableidx, rowidx, P, Prologue{}, mb);
@@ -2022,6 +2027,7 @@ int prologue_launch(const Dims& d, int N, const int64_t* indices, const Prologue
     if (rc_chk) return rc_chk;
   }
   ProfScope ps(TTX_PROF_PLAN, stream);
+  TTX_PLAN_ROUTE(mb ? TTX_ROUTE_MULTIBATCH : TTX_ROUTE_SINGLE_PROLOGUE);
   hipLaunchKernelGGL(mb_single_kernel<true>,
                      dim3((N + kOneWaves * kOneUnit - 1) / (kOneWaves * kOneUnit) + TTX_PLAN_XWG, d.T, nbatch),
                      dim3(kOneThreads), 0, stream, d, N, n_dev, indices, nullptr, nullptr, P, pg,
@@ -2117,6 +2123,43 @@ int ttx_lookup_prologue_multi(const ttx_geom* g, int32_t nbatch, int64_t nnz, co
   }
   return TTX_OK;
 }
+
+#ifdef TTX_TEST_HOOKS  // ---- the plan as the tests see it: libttx_hooks.so only (include/ttx_test_hooks.h) ----
+int ttx_debug_plan_layout(const ttx_geom* g, int64_t nnz, int64_t* out) {
+  ttx::Dims d;
+  const int rc = ttx::make_dims(g, &d);
+  if (rc != TTX_OK) return rc;
+  if (nnz < 0 || nnz >= (1ll << 31) || !out) TTX_FAIL(TTX_EINVAL, "ttx_debug_plan_layout: nnz=%lld out of range, or out is NULL", (long long)nnz);
+  int* const base = (int*)(uintptr_t)(1u << 20);  // (never dereferenced: carve_plan only adds to it)
+  const ttx::Plan P = ttx::carve_plan(d, nnz, base);
+  for (int i = 0; i < TTX_PLAN_LAYOUT_INTS; ++i) out[i] = 0;
+  auto put = [&](int k, const void* p, long long len) {
+    out[2 * k] = (int64_t)((const int*)p - base);
+    out[2 * k + 1] = (int64_t)len;
+  };
+  put(TTX_PLAN_HDR, P.hdr, 64);
+  put(TTX_PLAN_CHUNK_REC, P.chunk_rec, 4ll * P.max_chunks);
+  put(TTX_PLAN_LREC, P.lrec, 4ll * nnz);
+  put(TTX_PLAN_LROW, P.lrow, nnz);
+  put(TTX_PLAN_CHUNK_OFF, P.chunk_off, (long long)d.S[1] + 1);
+  put(TTX_PLAN_CNT, P.cnt, (long long)(P.sid[0] - P.cnt));  // (carve_plan hands out sid[0] right behind it)
+  for (int t = 0; t < d.T; ++t) {
+    const int k = TTX_PLAN_CORE0 + TTX_PLAN_PER_CORE * t;
+    put(k + 0, P.sid[t], nnz);
+    put(k + 1, P.perm[t], nnz);
+    put(k + 2, P.ipos[t], nnz);
+    put(k + 3, P.off[t], (long long)d.S[t] + 1);
+    for (int i = 0; i < 3; ++i) put(k + 4 + i, P.scratch[t][i], nnz);
+  }
+  out[TTX_PLAN_LAYOUT_MC] = P.MC;
+  out[TTX_PLAN_LAYOUT_MC + 1] = P.max_chunks;
+  out[TTX_PLAN_LAYOUT_MC + 2] = d.T;
+  out[TTX_PLAN_LAYOUT_MC + 3] = (int64_t)ttx::plan_bytes(d, nnz);
+  return TTX_OK;
+}
+
+int ttx_debug_plan_route(void) { return ttx::g_plan_route; }
+#endif  // TTX_TEST_HOOKS
 
 size_t ttx_plan_bytes(const ttx_geom* g, int64_t nnz) {
   ttx::Dims d;

@@ -1131,9 +1131,18 @@ __global__ __launch_bounds__(kReduceThreads, TTX_REDUCE_WAVES) void reduce_apply
     else sum_rows4(pc, sl, beg, end, red, IotaRow{}, ap);
     return;
   }
+  // (slice sizes that are no multiple of 4: one thread per element.  The rows are summed in blocks of kOwnerBlock, block sums
+  //  into the total: a hot slice stays with this owner too, and ONE running fp32 sum of its tens of thousands of same-sign rows
+  //  drifted 15 default bounds from float64 at 65,536 rows -- tests/test_plan_routes_gpu.py.  Up to kOwnerBlock rows: the sum it was.)
+  constexpr int kOwnerBlock = 256;
   for (int e = tid; e < sl; e += nthreads) {
     float g = 0.f;
-    for (int i = beg; i < end; ++i) g += pc[(list ? (size_t)list[i] : (size_t)i) * sl + e];
+    for (int i0 = beg; i0 < end; i0 += kOwnerBlock) {
+      const int i1 = min(end, i0 + kOwnerBlock);
+      float part = 0.f;
+      for (int i = i0; i < i1; ++i) part += pc[(list ? (size_t)list[i] : (size_t)i) * sl + e];
+      g += part;
+    }
     if (optim == TTX_OPTIM_DENSE) {
       dw[base + e] = g;
     } else {

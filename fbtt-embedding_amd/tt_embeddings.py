@@ -83,6 +83,8 @@ def hooks_lib():
         _hooks.ttx_debug_skip.argtypes = [i32]
         _hooks.ttx_debug_cache_fwd.argtypes = [i32]
         _hooks.ttx_debug_stamps.argtypes = [C.c_void_p]
+        _hooks.ttx_debug_plan_layout.argtypes = [C.POINTER(_Geom), C.c_int64, C.POINTER(C.c_int64)]
+        _hooks.ttx_debug_plan_route.argtypes = []
     _lib = _hooks
     return _hooks
 
@@ -1227,6 +1229,49 @@ def debug_cache_fwd(lookup_groups: int) -> None:
 def debug_stamps(ptr: Optional[int]) -> None:
     _check(hooks_lib().ttx_debug_stamps(C.c_void_p(ptr or None)))
     _knobs_changed()
+
+
+class test_library:
+    """`with test_library():` -- every call of the block goes to libttx_hooks.so whatever the knobs say (the plan tests: the
+    route id of debug_plan_route() belongs to the library that built the plan); afterwards the usual routing applies again."""
+
+    def __enter__(self):
+        hooks_lib()
+        return _hooks
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = _hooks if _hooks.ttx_debug_state() else _product
+
+
+PLAN_ARRAYS = ("hdr", "chunk_rec", "lrec", "lrow", "chunk_off", "cnt")
+PLAN_CORE_ARRAYS = ("sid", "perm", "ipos", "off", "scratch0", "scratch1", "scratch2")
+
+
+def debug_plan_layout(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, nnz) -> dict:
+    """Test helper (ttx_debug_plan_layout): {array: (offset, length) in int32 units of Plan.buf} for PLAN_ARRAYS and, per core t,
+    (name, t) for PLAN_CORE_ARRAYS; plus "MC", "max_chunks", "T", "bytes"."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    out = (C.c_int64 * 72)()
+    _check(hooks_lib().ttx_debug_plan_layout(C.byref(g), int(nnz), out))
+    _knobs_changed()
+    v = [int(x) for x in out]
+    lay = {name: (v[2 * k], v[2 * k + 1]) for k, name in enumerate(PLAN_ARRAYS)}
+    lay.update(MC=v[68], max_chunks=v[69], T=v[70], bytes=v[71])
+    for t in range(lay["T"]):
+        for j, name in enumerate(PLAN_CORE_ARRAYS):
+            k = len(PLAN_ARRAYS) + len(PLAN_CORE_ARRAYS) * t + j
+            lay[(name, t)] = (v[2 * k], v[2 * k + 1])
+    return lay
+
+
+def debug_plan_route() -> int:
+    """Test helper (ttx_debug_plan_route): the route id of the last plan the TEST library built (include/ttx_test_hooks.h
+    TTX_ROUTE_*; 0: none yet).  Build the plan inside `with test_library():`."""
+    if _hooks is None:
+        hooks_lib()
+        _knobs_changed()
+    return int(_hooks.ttx_debug_plan_route())
 
 
 def debug_tiles(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> dict:

@@ -29,6 +29,35 @@ int ttx_debug_cache_fwd(int32_t lookup_groups);
 /* (scripts/phase_times.py) device buffer receiving 16 int64 wall-clock stamps per backward work-group; NULL = off */
 int ttx_debug_stamps(void* device_buffer);
 
+/* ---- the lookup plan, as the tests see it (tests/test_plan_routes_gpu.py; no knob: neither changes what the library does) ---- */
+/* Where carve_plan (csrc/ttx_plan.hip) puts every array of a plan of `nnz` lookups, in ints from the start of the buffer:
+ * out[2 k] = offset, out[2 k + 1] = length of array k; k = TTX_PLAN_HDR .. TTX_PLAN_CNT, then per core t < TTX_MAX_CORES
+ * TTX_PLAN_CORE0 + TTX_PLAN_PER_CORE * t + {0 sid, 1 perm, 2 ipos, 3 off, 4..6 scratch} (zeros for t >= T); behind the
+ * pairs out[TTX_PLAN_LAYOUT_MC] = lookups per chunk, [+1] = max_chunks, [+2] = T, [+3] = ttx_plan_bytes.  The offsets are
+ * carve_plan's own: the function calls it on a made-up base address. */
+#define TTX_PLAN_HDR 0
+#define TTX_PLAN_CHUNK_REC 1
+#define TTX_PLAN_LREC 2
+#define TTX_PLAN_LROW 3
+#define TTX_PLAN_CHUNK_OFF 4
+#define TTX_PLAN_CNT 5
+#define TTX_PLAN_CORE0 6
+#define TTX_PLAN_PER_CORE 7
+#define TTX_PLAN_LAYOUT_MC 68
+#define TTX_PLAN_LAYOUT_INTS 72
+int ttx_debug_plan_layout(const ttx_geom* g, int64_t nnz, int64_t* out);
+/* The route the LAST plan build of this process took (a plain global of the test library, set where plan_build,
+ * plan_build_mb, plan_build_batches and prologue_launch choose); 0 = none yet. */
+#define TTX_ROUTE_TINY 1            /* plan_small_kernel */
+#define TTX_ROUTE_SINGLE 2          /* mb_single_kernel<false> */
+#define TTX_ROUTE_SINGLE_PROLOGUE 3 /* mb_single_kernel<true>: the lookup prologue of one batch */
+#define TTX_ROUTE_UNITS 4           /* mb_count / mb_scatter on wave units */
+#define TTX_ROUTE_WIDE 0            /* + bits: one wide digit of 10 / 11 / 12 bits -> 10, 11, 12 */
+#define TTX_ROUTE_GROUPED 10        /* + bits: a wide digit per table group -> 20, 21 */
+#define TTX_ROUTE_MULTIPASS 30      /* + the number of 8-bit passes -> 31, 32, 33, 34 */
+#define TTX_ROUTE_MULTIBATCH 40     /* several batches in one launch (ttx_lookup_prologue_multi, plan_build_batches) */
+int ttx_debug_plan_route(void);
+
 #ifdef __cplusplus
 }
 #endif

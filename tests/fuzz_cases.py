@@ -18,6 +18,7 @@ import torch
 
 import gen_inputs as G
 import oracle_lib as O
+import plan_ref as PR
 import tt_ref64 as R
 from util import ATOL_SCALE, RTOL, assert_adagrad_close, assert_close
 
@@ -121,7 +122,8 @@ def run_plan_cases(seed=0, max_cases=None, budget=None):
         ref_g = O.tt_backward(g, O.OPTIM_DENSE, B, D, 0, 0, idx, rowidx, tableidx, d_out, [x.copy() for x in cores])
         Lt = t(np.array([int(np.prod(p[k + 1:])) for k in range(T)], dtype=np.int64))
         gc = [t(x) for x in cores]
-        if tables > 1 and rs.rand() < 0.5:
+        by_prologue = tables > 1 and rs.rand() < 0.5
+        if by_prologue:
             ri, ti, plan = E.lookup_prologue(t(idx), t(off), tables, p, q, r)
             routes["prologue"] = routes.get("prologue", 0) + 1
         else:
@@ -209,8 +211,8 @@ def run_plan_cases(seed=0, max_cases=None, budget=None):
                 if f <= 1.0:
                     raise
                 ada(f)
-        S = tables * max(p)
-        route = "tiny" if nnz <= 1024 and E_ <= 2**32 else ("single" if S <= 256 and nnz <= 16384 else ("units" if S <= 256 else ("wide" if S <= 2048 else "multi-pass")))
+        route = PR.route_family(PR.route(PR.Geom(tables, p), nnz, int(plan.buf[:8].view(torch.int32)[1]), entry="prologue" if by_prologue else "build",
+                                         nb=tables * B))
         routes[route] = routes.get(route, 0) + 1
         n += 1
         E.debug_lds_budget(0)

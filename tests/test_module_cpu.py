@@ -89,7 +89,8 @@ def test_product_library_has_no_test_knobs():
 
     hooks_hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ttx_test_hooks.h")).read(), flags=re.S)
     knobs = sorted(set(re.findall(r"\b(ttx_[a-z0-9_]+)\s*\(", hooks_hdr)))
-    assert set(knobs) == {"ttx_set_chunk", "ttx_debug_lds_budget", "ttx_debug_skip", "ttx_debug_cache_fwd", "ttx_debug_stamps"}
+    assert set(knobs) == {"ttx_set_chunk", "ttx_debug_lds_budget", "ttx_debug_skip", "ttx_debug_cache_fwd", "ttx_debug_stamps",
+                          "ttx_debug_plan_layout", "ttx_debug_plan_route"}  # (the last two change nothing: how the plan tests see a plan)
     so = os.path.join(ROOT, "fbtt-embedding_amd", "libttx.so")
     exported = [ln.split()[-1] for ln in subprocess.check_output(["nm", "-D", "--defined-only", so], text=True).splitlines()]
     assert exported and all(sym.startswith("ttx_") for sym in exported), [x for x in exported if not x.startswith("ttx_")]
@@ -107,6 +108,16 @@ def test_product_library_has_no_test_knobs():
     finally:
         E.debug_skip(0)
     assert E.lib() is E._product
+    # the plan tests' window: inside the block calls go to the test library, the route id is its own, and nothing sticks afterwards
+    assert E.debug_plan_route() == E._hooks.ttx_debug_plan_route() and E.lib() is E._product
+    with E.test_library() as L:
+        assert L is E._hooks and E.lib() is E._hooks
+    assert E.lib() is E._product and E._hooks.ttx_debug_state() == 0
+    lay = E.debug_plan_layout(1, [7, 6, 5], [2, 3, 2], [1, 4, 5, 1], 1000)
+    assert E.lib() is E._product and lay["T"] == 3 and lay["bytes"] == E.lib().ttx_plan_bytes(ctypes.byref(E._geom(1, [7, 6, 5], [2, 3, 2], [1, 4, 5, 1])), 1000)
+    spans = sorted(v for k, v in lay.items() if isinstance(v, tuple))
+    assert all(a[0] + a[1] <= b[0] for a, b in zip(spans, spans[1:])) and spans[-1][0] + spans[-1][1] <= lay["bytes"] // 4, "the arrays overlap"
+    assert lay["lrec"][1] == 4000 and lay[("off", 1)][1] == 7 and lay["chunk_rec"][1] == 4 * lay["max_chunks"]
 
 
 def test_importing_the_module_leaves_torch_untouched():

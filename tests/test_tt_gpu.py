@@ -213,20 +213,38 @@ def test_large_batch_uses_the_global_memory_plan():
 def test_plan_paths_vs_oracle(tables, p, B, pf):
     """every route through the lookup plan (ttx_plan.hip): single launch (all sorts one 8-bit pass,
     N <= 16384) is what the other tests take; here the wide-digit single pass (256 < slices <= 4096,
-    up to 96 work-groups), multi-pass sorts, the separate scan launch and the finish launch.  Forward, dense grads and fused SGD against the oracle."""
+    up to 96 work-groups), multi-pass sorts, the separate scan launch and the finish launch.  Forward, dense grads and fused SGD against the oracle.
+
+    An array on which the fp32 oracle is ITSELF more than a default bound from the float64 reference (tests/tt_ref64.py) is compared
+    with float64 instead, at the same tolerance: there the oracle's value is its own rounding, not the operation's.  One array is:
+    the SGD core 2 at 1.2 M lookups -- 24,000 rows per slice in ONE running fp32 sum, 1.69 default bounds from float64, which only
+    a kernel adding in the same order could match (reduce_apply's scalar owner did until it summed in blocks; every other array of
+    these cases has its oracle within 0.72)."""
+    import tt_ref64 as R
+
     q, r = [2, 3, 2], [1, 4, 5, 1]
     E_, D = int(np.prod(np.array(p, dtype=np.int64))), int(np.prod(q))
     idx, off = G.make_bags(5 + B, B, E_, pf, 1, tables)
     c = dict(tables=tables, T=3, p=p, q=q, r=r, B=B, D=D, indices=idx, offsets=off,
              cores=G.make_cores(6 + B, tables, p, q, r, "signed"), d_out=G.make_grad(7, tables, B, D))
+    rowidx, tableidx = O.rowidx_from_offsets(off, tables)
+    ref = R.forward_backward(tables, p, q, r, B, idx, rowidx, tableidx, c["cores"], c["d_out"])
+    ref["cores"] = R.sgd_step(c["cores"], ref["grads"], LR)
+
+    def reference(oracle, ref64, what):
+        u = R.default_units(oracle, ref64)
+        if u > 1.0:
+            print(f"[plan-paths] {what}: the oracle is {u:.3f} default bounds from float64 -> compared with float64")
+        return ref64 if u > 1.0 else oracle
+
     for mode in ("dense", "sgd"):
         got, orc = run_case(c, mode, plan_shared=True), oracle_case(c, mode)
-        assert_close(got["out"], orc["out"], f"plan {p} out")
+        assert_close(got["out"], reference(orc["out"], ref["out"], f"plan {p} out"), f"plan {p} out")
         for k in range(3):
             if mode == "dense":
-                assert_close(got["grads"][k], orc["grads"][k], f"plan {p} grad{k}")
+                assert_close(got["grads"][k], reference(orc["grads"][k], ref["grads"][k], f"plan {p} grad{k}"), f"plan {p} grad{k}")
             else:
-                assert_close(got["cores"][k], orc["cores"][k], f"plan {p} sgd core{k}")
+                assert_close(got["cores"][k], reference(orc["cores"][k], ref["cores"][k], f"plan {p} sgd core{k}"), f"plan {p} sgd core{k}")
 
 
 def test_wide_digit_plan_declines_more_than_2_to_18_full_chunks():
