@@ -785,6 +785,23 @@ int sort_pairs_desc(int64_t H, const int64_t* keys_in, const int64_t* vals_in, c
   return TTX_OK;
 }
 
+// (ttx_internal.h) the populate's sort + mark; ws as the first populate_sort_ws_bytes(H) bytes of ttx_cache_populate's workspace
+size_t populate_sort_ws_bytes(int64_t H) {
+  int WT, U;
+  unit_shape(H, &WT, &U);
+  return 4 * align_up((size_t)H * 8) + align_up((size_t)256 * U * 4) + 2048;
+}
+
+int populate_sort_mark(int64_t H, int64_t* hashtbl, int64_t* cache_freq, int32_t* cache_state, int64_t cache_size,
+                       int keep_state, char* ws, int64_t** sorted_keys, hipStream_t st) {
+  const int rc = sort_pairs_desc(H, cache_freq, hashtbl, ws, nullptr, sorted_keys, st, -1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(mark_popular_kernel, dim3((unsigned)((H + kCT - 1) / kCT)), dim3(kCT), 0, st, (int32_t)H,
+                     cache_size, *sorted_keys, hashtbl, cache_freq, cache_state, keep_state);
+  TTX_HIP(hipGetLastError());
+  return TTX_OK;
+}
+
 
 }  // namespace ttx
 
@@ -1746,14 +1763,9 @@ int ttx_cache_populate_f(const ttx_geom* g, const float* const* tt_cores, int64_
     TTX_FAIL(TTX_EWORKSPACE, "cache_populate workspace too small");
   char* ws = (char*)workspace;
   int64_t* sorted_keys = nullptr;
-  rc = sort_pairs_desc(H, cache_freq, hashtbl, ws, nullptr, &sorted_keys, st, -1);
+  rc = populate_sort_mark(H, hashtbl, cache_freq, cache_state, cache_size, flags & TTX_POPULATE_REFERENCE_EXACT, ws, &sorted_keys, st);
   if (rc) return rc;
-  int WT, U;
-  unit_shape(H, &WT, &U);
-  char* rows_ws = ws + 4 * align_up((size_t)H * 8) + align_up((size_t)256 * U * 4) + 2048;
-  hipLaunchKernelGGL(mark_popular_kernel, dim3((unsigned)((H + kCT - 1) / kCT)), dim3(kCT), 0, st, (int32_t)H,
-                     cache_size, sorted_keys, hashtbl, cache_freq, cache_state, flags & TTX_POPULATE_REFERENCE_EXACT);
-  TTX_HIP(hipGetLastError());
+  char* rows_ws = ws + populate_sort_ws_bytes(H);
   if (cache_size == 0) return TTX_OK;
   if (!cache_weight) TTX_FAIL(TTX_EINVAL, "cache_weight is NULL");
   return ttx_tt_rows(g, D, cache_size, sorted_keys, nullptr, tt_cores, cache_weight, rows_ws,

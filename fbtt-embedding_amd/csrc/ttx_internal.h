@@ -220,6 +220,14 @@ size_t sort_pairs_ws_bytes(int64_t n);
 int sort_pairs_desc(int64_t n, const int64_t* keys_in, const int64_t* vals_in, char* ws, int64_t** keys_sorted,
                     int64_t** vals_sorted, hipStream_t st, int passes);
 
+// cache_populate's first half (ttx_cache.hip): the sort of the slots by frequency and mark_popular_kernel on the sorted keys --
+// the top cache_size keys get their cache rows, the others leave the table; an empty slot among the first cache_size
+// becomes key 0.  ws: populate_sort_ws_bytes(H).  -> the sorted keys inside ws (what is then decompressed).  Shared by the
+// one-table populate and the populate over several tables (ttx_cache_tables.hip), whose keys differ only in what they mean.
+size_t populate_sort_ws_bytes(int64_t H);
+int populate_sort_mark(int64_t H, int64_t* hashtbl, int64_t* cache_freq, int32_t* cache_state, int64_t cache_size,
+                       int keep_state, char* ws, int64_t** sorted_keys, hipStream_t st);
+
 // ------------------------------------------------------------ profiling ----
 void prof_begin(int which, hipStream_t s);
 void prof_end(int which, hipStream_t s);

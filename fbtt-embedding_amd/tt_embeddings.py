@@ -16,8 +16,9 @@ bench.py): `make_plan` (share the lookup plan between forward and backward; `ded
 the batch share one contraction),
 `profile_*` (live kernel timings), `lib()` (the loaded ctypes library), the pooling modes' `bag_mean_scale`, `tt_rows_p`,
 `bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, the unpooled lookup's `rows_expand` /
-`rows_collect` (and, with a live cache, `preprocess_indices_async`, `rows_place` / `rows_pick`), and `bags_merge` (the per-table
-batches of a mixed-cardinality group -> one table-major batch, one launch).
+`rows_collect` (and, with a live cache, `preprocess_indices_async`, `rows_place` / `rows_pick`), `bags_merge` (the per-table
+batches of a mixed-cardinality group -> one table-major batch, one launch), and the row cache over several tables' `table_keys`,
+`table_keys_split` and `cache_populate_tables`.
 """
 import ctypes as C
 import os
@@ -182,6 +183,13 @@ def _load(path):
     L.ttx_cache_backward_sgd_n.argtypes = [i64, vp, i32, vp, vp, vp, f32, vp, vp]
     L.ttx_cache_backward_dense_n.argtypes = [i64, vp, i32, vp, vp, vp, i64, vp, vp]
     L.ttx_cache_backward_rowwise_adagrad_approx_n.argtypes = [i64, vp, i32, vp, vp, vp, f32, f32, vp, vp, vp]
+    # row cache over several tables: (table, index) <-> key, the populate of any table's rows, the gather behind a device-side split
+    L.ttx_table_keys.argtypes = [i64, vp, i32, i64, vp, i64, vp, i64, vp, vp, vp]
+    L.ttx_table_keys_split.argtypes = [i64, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.ttx_cache_populate_t_workspace_bytes.restype = C.c_size_t
+    L.ttx_cache_populate_t_workspace_bytes.argtypes = [G, i64, i64, i32]
+    L.ttx_cache_populate_t.argtypes = [G, vp, i64, vp, vp, vp, i64, i32, vp, i64, i32, vp, sz, vp]
+    L.ttx_cache_forward_n.argtypes = [i32, i64, vp, vp, vp, i32, vp, vp, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
@@ -612,6 +620,89 @@ def cache_populate(num_embeddings: int, tt_p_shapes, tt_q_shapes, tt_ranks, tt_c
                                        ws.data_ptr(), ws.numel(), st))
 
 
+def table_keys(indices: torch.Tensor, offsets: torch.Tensor, num_tables: int, key_stride: int,
+               hashtbl: Optional[torch.Tensor] = None, cache_freq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Not in the reference: the keys of a table-major batch in the row cache over several tables (include/ttx.h, "row cache
+    over several tables") -- keys[n] = indices[n] + table(n) * key_stride, the table read off the batch's bag `offsets`
+    (num_tables * B + 1 entries, closing entry included).  With `hashtbl` / `cache_freq` the same launch counts the keys, as
+    update_cache_state(keys, hashtbl, cache_freq) would.  -> keys [nnz] int64."""
+    dev = _dev(indices)
+    indices, offsets = _i64(indices, "indices"), _i64(offsets, "offsets")
+    nnz, nb = indices.numel(), offsets.numel() - 1
+    if num_tables <= 0 or nb <= 0 or nb % num_tables != 0 or offsets.device != dev:
+        raise RuntimeError(f"tt_embeddings: offsets must hold num_tables * B + 1 entries on {dev}, got {offsets.numel()} for "
+                           f"{num_tables} tables on {offsets.device}")
+    count = hashtbl is not None or cache_freq is not None
+    if count:
+        if hashtbl is None or cache_freq is None or hashtbl.numel() <= 0 or hashtbl.numel() != cache_freq.numel():
+            raise RuntimeError("tt_embeddings: hashtbl must be non-empty and match cache_freq")
+        _i64(hashtbl, "hashtbl"), _i64(cache_freq, "cache_freq")
+        if hashtbl.device != dev or cache_freq.device != dev:
+            raise RuntimeError(f"tt_embeddings: hashtbl and cache_freq must be on {dev}")
+    keys = torch.empty_like(indices)
+    if nnz == 0:
+        return keys
+    with _guard(dev):
+        _check(lib().ttx_table_keys(nnz, indices.data_ptr(), num_tables, nb // num_tables, offsets.data_ptr(), int(key_stride),
+                                    keys.data_ptr(), hashtbl.numel() if count else 0, hashtbl.data_ptr() if count else None,
+                                    cache_freq.data_ptr() if count else None, _stream(dev)))
+    return keys
+
+
+def table_keys_split(keys: torch.Tensor, bagrow: Optional[torch.Tensor], num_tables: int, B: int, key_stride: int,
+                     n_dev: Optional[torch.Tensor] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Not in the reference: the inverse of table_keys on the first *n_dev entries (one int32 on the device; None: all).  With
+    `bagrow` (flat bag rows table * B + b: the prow of preprocess_indices_async over keys) -> (indices, tableidx, rowidx) of
+    those entries, what make_plan(n_dev=) takes for the misses; with bagrow None the table is keys // key_stride and rowidx is
+    None.  Entries at and beyond the count are not written (uninitialised)."""
+    dev = _dev(keys)
+    keys = _i64(keys, "keys")
+    n = keys.numel()
+    out_i, out_t = torch.empty_like(keys), torch.empty_like(keys)
+    out_r = None
+    if bagrow is not None:
+        bagrow = _i64(bagrow, "bagrow")
+        if bagrow.numel() < n or bagrow.device != dev:
+            raise RuntimeError(f"tt_embeddings: bagrow must hold one bag row per key on {dev}")
+        out_r = torch.empty_like(keys)
+    if n == 0:
+        return out_i, out_t, out_r
+    with _guard(dev):
+        _check(lib().ttx_table_keys_split(n, None if n_dev is None else _skip_ptr(n_dev, dev), num_tables, B, int(key_stride),
+                                          keys.data_ptr(), None if bagrow is None else bagrow.data_ptr(), out_i.data_ptr(),
+                                          out_t.data_ptr(), None if out_r is None else out_r.data_ptr(), _stream(dev)))
+    return out_i, out_t, out_r
+
+
+def cache_populate_tables(num_tables: int, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores, hashtbl, cache_freq, cache_state,
+                          cache_weight, key_stride: int, reference_exact: bool = False) -> None:
+    """Not in the reference: cache_populate for the row cache over the `num_tables` tables of one table-batched bag, whose
+    hash table holds keys table * key_stride + index (ttx_cache_populate_t): the cache_size most frequent keys get the cache
+    rows, each decompressed from its own table's cores."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(cache_weight)
+    cores = _cores(list(tt_cores), g)
+    H = hashtbl.numel()
+    if H <= 0 or H != cache_freq.numel() or H < cache_weight.size(0):
+        raise RuntimeError("tt_embeddings: need 0 < hashtbl.numel() == cache_freq.numel() >= cache_size")
+    _i64(hashtbl, "hashtbl"), _i64(cache_freq, "cache_freq")
+    if cache_state.dtype != torch.int32 or cache_state.numel() != H:
+        raise RuntimeError("tt_embeddings: cache_state must be int32[hashtbl_size]")
+    cw = cache_weight.detach()
+    if cw.dtype != torch.float32 or not cw.is_contiguous():
+        raise RuntimeError("tt_embeddings: cache_weight must be contiguous float32")
+    cs, D = cw.size(0), cw.size(1)
+    lb = lib()
+    st = _stream(dev)
+    nb = lb.ttx_cache_populate_t_workspace_bytes(C.byref(g), H, cs, D)
+    ws = _workspace(dev, st, nb)
+    with _guard(dev):
+        _check(lb.ttx_cache_populate_t(C.byref(g), _ptr_array(cores), H, hashtbl.data_ptr(), cache_freq.data_ptr(),
+                                       cache_state.data_ptr(), cs, D, cw.data_ptr(), int(key_stride),
+                                       1 if reference_exact else 0, ws.data_ptr(), ws.numel(), st))
+
+
 def preprocess_indices_sync(colidx: torch.Tensor, offsets: torch.Tensor, num_tables: int, warmup: bool,
                             hashtbl: torch.Tensor, cache_state: torch.Tensor,
                             update_cache_freq: Optional[torch.Tensor] = None
@@ -699,8 +790,10 @@ def _check_cached_args(nnz: int, cache_locations: torch.Tensor, rowidx: torch.Te
 
 
 def cache_forward(B: int, nnz: int, cache_locations: torch.Tensor, rowidx: torch.Tensor, cache_weight: torch.Tensor,
-                  output: torch.Tensor) -> None:
-    """tt_embeddings.cpp:97-103: output[rowidx[n], :] += cache_weight[cache_locations[n], :]."""
+                  output: torch.Tensor, skip_dev: Optional[torch.Tensor] = None) -> None:
+    """tt_embeddings.cpp:97-103: output[rowidx[n], :] += cache_weight[cache_locations[n], :].  `skip_dev` (trailing keyword, not
+    in the reference): one int32 on the device, the number of LEADING entries of cache_locations / rowidx that are not cached --
+    the arrays are the whole partitioned batch of `nnz` lookups and the gather works on [*skip_dev, nnz) (ttx_cache_forward_n)."""
     dev = _dev(output)
     if B <= 0:
         raise RuntimeError("tt_embeddings: B must be > 0")  # cu:1549
@@ -708,6 +801,12 @@ def cache_forward(B: int, nnz: int, cache_locations: torch.Tensor, rowidx: torch
         return
     _check_cached_args(nnz, cache_locations, rowidx)
     cw = cache_weight.detach()
+    if skip_dev is not None:
+        with _guard(dev):
+            _check(lib().ttx_cache_forward_n(B, nnz, _skip_ptr(skip_dev, dev), cache_locations.data_ptr(),
+                                             _i64(rowidx, "rowidx").data_ptr(), cw.size(1), cw.data_ptr(), output.data_ptr(),
+                                             _stream(dev)))
+        return
     with _guard(dev):
         _check(lib().ttx_cache_forward(B, nnz, cache_locations.data_ptr(), _i64(rowidx, "rowidx").data_ptr(), cw.size(1),
                                        cw.data_ptr(), output.data_ptr(), _stream(dev)))

@@ -30,6 +30,9 @@ Deliberate differences (each is a superset or a fix):
     `offsets=None`; the padding is dropped on the device (`bags_compact`) in front of the lookup;
   * nn.Embedding's unpooled lookup: the module `TTEmbedding` (one row per index of an index tensor of any shape, `padding_idx`;
     TTRowsLookupFunction below), on the ctypes route;
+  * one row cache over the tables of a table-batched bag: `TableBatchedTTEmbeddingBag(num_tables > 1, use_cache=True)` (the
+    reference asserts one table, :456) keys one hash table / cache_weight by table * prod(tt_p_shapes) + index
+    (TTTablesCachedLookupFunction below, DESIGN.md 4.13), on the ctypes route;
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -558,6 +561,70 @@ class TTRowsCachedLookupFunction(torch.autograd.Function):
         return tuple(head + list(grads))
 
 
+class TTTablesCachedLookupFunction(torch.autograd.Function):
+    """The table-batched bag lookup with a LIVE row cache over several tables (TableBatchedTTEmbeddingBag(num_tables > 1,
+    use_cache=True) after cache_populate()), beside TTRowsCachedLookupFunction and of its shape.  One cache
+    serves all tables, keyed by key = table * key_stride + index; bags are addressed by their flat row table * B + b, the
+    output and its gradient viewed as [num_tables * B, D].  Forward: table_keys, preprocess_indices_async over the keys as ONE
+    table of num_tables * B bags (frequency update folded in, hits behind the misses, the split point on the device),
+    table_keys_split of the misses back to (index, table, bag row), the plan of the misses (make_plan(n_dev=split point)), their
+    contraction and pooling (tt_forward) and cache_forward(skip_dev=split point) for the hits.  Backward: the fused SGD /
+    Adagrad or dense backward on the plan, and the cache rows' update with rowidx = the flat bag rows and skip_dev = the split
+    point: SGD, row-wise Adagrad, or the dense gradient of cache_weight (returned in its slot).  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, B: int, D: int, num_tables: int, key_stride: int, tt_p_shapes: List[int], tt_q_shapes: List[int],
+                tt_ranks: List[int], L: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor, hashtbl: torch.Tensor,
+                cache_state: torch.Tensor, cache_freq: Optional[torch.Tensor], det: Optional[bool], optimizer: OptimType,
+                learning_rate: float, eps: float, sparse: bool, cache_optimizer_state: Optional[torch.Tensor],
+                cache_weight: torch.Tensor, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
+        n = indices.numel()
+        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
+        ctx.B, ctx.D, ctx.nt, ctx.n, ctx.det = B, D, num_tables, n, det
+        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
+        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        keys = _engine.table_keys(indices, offsets, num_tables, key_stride)
+        pkey, prow, ploc, n_tt = _engine.preprocess_indices_async(keys, offsets, hashtbl, cache_state, cache_freq)
+        # (prow: the flat bag row table * B + b -- the preprocess saw one table of num_tables * B bags)
+        idx, tableidx, rowidx = _engine.table_keys_split(pkey, prow, num_tables, B, key_stride, n_dev=n_tt)
+        plan = _engine.make_plan(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, n, idx, tableidx, rowidx, n_dev=n_tt)
+        output = _engine.tt_forward(1000, num_tables, B, D, tt_p_shapes, tt_q_shapes, tt_ranks, L, n, idx, rowidx, tableidx,
+                                    list(tt_cores), plan=plan)
+        _engine.cache_forward(num_tables * B, n, ploc, prow, cache_weight, output, skip_dev=n_tt)
+        ctx.plan = plan
+        ctx.save_for_backward(L, idx, rowidx, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight)
+        return output
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        L, idx, rowidx, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight = ctx.saved_tensors
+        p, q, ranks = ctx.geometry
+        n, D = ctx.n, ctx.D
+        cores = list(ctx.tt_cores)
+        head: List[Optional[torch.Tensor]] = [None] * 21
+        d_output = d_output.contiguous()
+        d_flat = d_output.view(ctx.nt * ctx.B, D)
+        det = ctx.det
+        auto = getattr(_engine, "_use_sorted", None)
+        if det is None and auto is not None:  # "auto" looks at the BATCH (misses + hits), as TTLookupFunction.backward does
+            det = auto(None, n, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
+        if ctx.sparse:
+            if ctx.optimizer in _SGD_LIKE:
+                _engine.tt_sgd_backward(1000, D, ctx.learning_rate, p, q, ranks, L, n, idx, rowidx, tableidx, d_output, cores,
+                                        plan=ctx.plan)
+                _engine.cache_backward_sgd(n, d_flat, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det, skip_dev=n_tt)
+            else:
+                _engine.tt_adagrad_backward(1000, D, ctx.learning_rate, ctx.eps, p, q, ranks, L, n, idx, rowidx, tableidx,
+                                            d_output, ctx.optimizer_state, cores, plan=ctx.plan)
+                _engine.cache_backward_rowwise_adagrad_approx(n, d_flat, ploc, prow, ctx.learning_rate, ctx.eps,
+                                                              cache_optimizer_state, cache_weight, deterministic=det, skip_dev=n_tt)
+            return tuple(head + [None] * len(cores))
+        grads = _engine.tt_dense_backward(1000, D, p, q, ranks, L, n, idx, rowidx, tableidx, d_output, cores, plan=ctx.plan)
+        head[19] = _engine.cache_backward_dense(n, d_flat, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det,
+                                                skip_dev=n_tt)
+        return tuple(head + list(grads))
+
+
 class _RowsAtPositionsFunction(torch.autograd.Function):
     """rows_expand / rows_collect around a lookup that returned the rows of the live positions only (TTEmbedding's dedup route
     with padding_idx, where the live count n has been read back): rows [n, D] -> out [N, D], zeros at the padding."""
@@ -650,7 +717,8 @@ def suggested_tt_shapes(n: int, d: int = 3, allow_round_up: bool = True) -> List
 class TableBatchedTTEmbeddingBag(nn.Module):
     """`num_tables` TT-compressed embedding tables of identical shape looked up
     in one pass (sum pooling -- or `mode="mean"` / `"max"` --, include_last_offset form: offsets has
-    num_tables*B + 1 entries, bags ordered table-major)."""
+    num_tables*B + 1 entries, bags ordered table-major).  `use_cache=True` with several tables (not in the reference): ONE LFU
+    row cache over all of them, keyed by table * prod(tt_p_shapes) + index."""
 
     __constants__ = ["num_tables", "num_embeddings", "embedding_dim", "tt_shape", "tt_rank"]
 
@@ -711,7 +779,6 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         device = torch.device(device)
         num_embeddings, embedding_dim = int(num_embeddings), int(embedding_dim)
         assert num_tables > 0 and num_embeddings > 0 and embedding_dim > 0
-        assert num_tables == 1 or not use_cache, "cannot use cache when num_tables != 1"
         tt_ranks = [int(x) for x in tt_ranks]
         nd = len(tt_ranks) + 1
         self.tt_p_shapes: List[int] = [int(x) for x in tt_p_shapes] if tt_p_shapes is not None \
@@ -759,8 +826,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         self.reset_parameters(weight_dist)
         self.use_cache = use_cache
         if use_cache:
-            cache_size = cache_size if cache_size > 0 else int(0.1 * num_embeddings)
-            hashtbl_size = hashtbl_size if hashtbl_size > 0 else num_embeddings
+            # num_tables > 1 (not in the reference, whose cache serves one table, :456): ONE cache over all tables, keyed by
+            # table * key_stride + index with key_stride = prod(tt_p_shapes) -- the cache_size hottest rows across the tables
+            # (DESIGN.md 4.13).  Same parameters, buffers and state_dict() keys as the one-table cached module.
+            cache_size = cache_size if cache_size > 0 else int(0.1 * num_tables * num_embeddings)
+            hashtbl_size = hashtbl_size if hashtbl_size > 0 else num_tables * num_embeddings
+            if num_tables > 1:
+                if hashtbl_size >= 2 ** 31:
+                    raise ValueError(f"hashtbl_size must stay below 2^31, got {hashtbl_size} (the default is num_tables * "
+                                     f"num_embeddings: pass a smaller hashtbl_size)")
+                if num_tables * self._key_stride() >= 2 ** 62:
+                    raise ValueError(f"the cache's key space num_tables * prod(tt_p_shapes) = {num_tables} * {self._key_stride()} "
+                                     f"does not fit 2^62")
             assert hashtbl_size >= cache_size
             self.register_buffer("hashtbl", torch.full((hashtbl_size,), -1, device=device, dtype=torch.int64))
             self.register_buffer("cache_freq", torch.zeros(hashtbl_size, device=device, dtype=torch.int64))
@@ -891,6 +968,28 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             _engine.tt_sgd_backward(1000, self.embedding_dim, float(lr), self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, self.L,
                                     n, colidx, rowidx, tableidx, diff, cores)
 
+    def _key_stride(self) -> int:
+        """the row cache over several tables keys a lookup by table * key_stride + index: prod(tt_p_shapes), the range the
+        index decode covers (>= num_embeddings)"""
+        return int(np.prod(np.asarray(self.tt_p_shapes, dtype=np.int64)))
+
+    def _tables_cache(self) -> bool:
+        """one row cache over several tables"""
+        return bool(self.use_cache) and self.num_tables > 1
+
+    def _count_keys(self, indices: torch.Tensor, offsets: torch.Tensor) -> None:
+        """several tables: the frequency table counts KEYS (offsets with their closing entry) -- one launch on the GPU
+        (table_keys with the count folded in), torch ops on CPU tensors (the tests' oracle engine)."""
+        if indices.numel() == 0:
+            return
+        if indices.is_cuda and getattr(_engine, "table_keys", None) is not None:
+            _engine.table_keys(indices, offsets, self.num_tables, self._key_stride(), self.hashtbl, self.cache_freq)
+            return
+        B = (offsets.numel() - 1) // self.num_tables
+        bounds = offsets[::B][1:self.num_tables].contiguous()  # the first position of tables 1 .. num_tables - 1
+        table = torch.bucketize(torch.arange(indices.numel(), dtype=torch.int64, device=indices.device), bounds, right=True)
+        _engine.update_cache_state((indices + table * self._key_stride()).contiguous(), self.hashtbl, self.cache_freq)
+
     def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1) -> None:
         """tt_embeddings_ops.py:800-814.  `write_back` (NOT in the reference; default 0 = its behaviour): cached rows are trained
         directly, and a populate decompresses every cache row anew from the cores -- what the cached copies learnt since the last
@@ -899,6 +998,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         for every cached key, through the ordinary forward / backward contraction), which moves the TT rows toward what the cache
         learnt -- an approximation (the cached keys share core slices: a few steps recover part of the difference, measured in
         tests/test_module_cpu.py), off by default."""
+        if self._tables_cache():
+            if write_back > 0.0:
+                raise NotImplementedError("cache_populate(write_back > 0) is not supported by the row cache over several tables")
+            populate = getattr(_engine, "cache_populate_tables", None)
+            if populate is None or not self.cache_weight.is_cuda:
+                raise NotImplementedError("the row cache over several tables is populated on the GPU only")
+            extra = {"reference_exact": True} if self.reference_exact_populate else {}
+            populate(self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), self.hashtbl,
+                     self.cache_freq, self.cache_state, self.cache_weight, self._key_stride(), **extra)
+            self.warmup = False
+            self._drop_prefetched()
+            return
         if self.use_cache and write_back > 0.0 and not self.warmup:
             self._write_back(write_back, write_back_steps)
         if self.use_cache:
@@ -909,7 +1020,17 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             self.warmup = False
             self._drop_prefetched()  # (a planned-ahead batch was split into hits / misses by the OLD cache contents)
 
-    def update_cache(self, indices: torch.Tensor) -> None:
+    def update_cache(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> None:
+        """count a batch in the frequency table.  Several tables: the cache counts keys table * key_stride + index, the table
+        read off the batch's `offsets` (the form forward() takes), which are then required."""
+        if self._tables_cache():
+            if indices.numel() == 0:
+                return
+            if offsets is None:
+                raise ValueError("update_cache(indices, offsets): the row cache over several tables needs the batch's offsets")
+            indices, offsets = self._normalise(indices, offsets)
+            self._count_keys(indices.contiguous(), offsets.contiguous())
+            return
         if self.use_cache:
             _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)
 
@@ -933,6 +1054,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         overlap does not apply: cache live, no C++ node, CPU tensors, empty batch, duplicate sharing, a module with padding_idx
         or 2-D indices (a prologue planned ahead would be over the uncompacted slots)."""
         if self.__dict__.get("padding_idx") is not None or offsets is None or indices.dim() != 1:
+            return False
+        if self._tables_cache():  # (the prologue planned ahead would count local indices, not keys)
             return False
         fast = _native_node()
         if (fast is None or not self.warmup or not indices.is_cuda or indices.numel() == 0 or self._dedup_may_share(indices.numel())
@@ -976,6 +1099,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         fast = _native_node()
         batches = list(batches)
         if self.__dict__.get("padding_idx") is not None or any(o is None or i.dim() != 1 for i, o in batches):
+            return False
+        if self._tables_cache():  # (the prologues planned ahead would count local indices, not keys)
             return False
         live = not self.warmup
         if (fast is None or not batches or self.__dict__.get("_split0", 0) > 1 or self._dedup_may_share(batches[0][0].numel())
@@ -1092,8 +1217,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         core 0 and its optimizer state: the same memory); the output [tables, k B, D / k] IS [tables, B, D]."""
         use_state = self.sparse and self.optimizer not in _SGD_LIKE
         optim = 2 if not self.sparse else (1 if use_state else 0)
-        if self.use_cache:  # (the frequency table counts the caller's indices, not the part lookups)
-            _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)
+        if self.use_cache and self.num_tables == 1:  # (the frequency table counts the caller's indices, not the part lookups;
+            _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)  # several tables: _forward_sum counted their keys)
         p, q, nt = self.tt_p_shapes, self.tt_q_shapes, self.num_tables
         vi, vo = _engine.split0_expand(indices, offsets, k, p[1] * p[2])
         Q = self.__dict__.get("_pad0", 0) or q[0]
@@ -1365,6 +1490,27 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             raise ValueError(f"offsets must describe num_tables * B bags, got {offsets.numel() - 1} bags for "
                              f"{self.num_tables} tables")
         fast = _native_node()
+        count_local = d["use_cache"]  # the route's own frequency update counts the indices as they are (one table)
+        if count_local and d["num_tables"] > 1:
+            # ONE row cache over all tables: the frequency table holds keys table * key_stride + index
+            count_local = False
+            if not self.warmup and indices.numel() > 0:
+                if not indices.is_cuda or getattr(_engine, "table_keys", None) is None:
+                    raise NotImplementedError("a live row cache over several tables serves GPU tensors only")
+                if per_sample_weights is not None:
+                    raise NotImplementedError("per_sample_weights with a live row cache over several tables")
+                use_state = self.sparse and self.optimizer not in _SGD_LIKE
+                return TTTablesCachedLookupFunction.apply(
+                    (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.num_tables, self._key_stride(),
+                    self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, self.L, indices.contiguous(), offsets.contiguous(),
+                    self.hashtbl, self.cache_state, self.cache_freq, d.get("deterministic_cache_update"), self.optimizer,
+                    self.learning_rate, self.eps, self.sparse, self.cache_optimizer_state if use_state else None,
+                    self.cache_weight, list(self.optimizer_state), *self.tt_cores)
+            if self.warmup:
+                # warm-up: the batch's keys are counted here (one extra launch), and the lookup runs on the existing routes
+                # with their own frequency update switched off
+                self._count_keys(indices.contiguous(), offsets.contiguous())
+                d["_pf_counted"] = True
         share = getattr(self, "dedup", False) and self.warmup and indices.is_cuda and indices.numel() > 0 \
             and per_sample_weights is None and getattr(_engine, "DedupPlan", None) is not None
         sample = False
@@ -1375,7 +1521,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             # plan of the distinct pairs (one work-group sorts the batch's keys), through the reference-shaped route
             indices, rowidx, tableidx, n_tt, cache_locations = _engine.preprocess_indices_sync(
                 indices, offsets, self.num_tables, True, self.hashtbl, self.cache_state,
-                *((self.cache_freq,) if self.use_cache else ()))
+                *((self.cache_freq,) if count_local else ()))
             rowidx._ttx_plan = _engine.make_plan(self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks,
                                                  n_tt, indices, tableidx, rowidx, dedup=True)
             if sample:  # the map's header holds the number of distinct pairs (one read-back per sampling period)
@@ -1444,17 +1590,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         if prologue is not None and self.warmup and indices.numel() > 0:
             # cache not live: frequency update, offsets -> bag rows and the lookup plan in one native call
             rowidx, tableidx, plan = prologue(indices, offsets, self.num_tables, self.tt_p_shapes, self.tt_q_shapes,
-                                              self.tt_ranks, self.hashtbl if self.use_cache else None,
-                                              self.cache_freq if self.use_cache else None)
+                                              self.tt_ranks, self.hashtbl if count_local else None,
+                                              self.cache_freq if count_local else None)
             rowidx._ttx_plan = plan  # picked up by TTLookupFunction.forward
             n_tt, cache_locations = indices.numel(), None
-        elif self.use_cache and getattr(_engine, "FUSED_CACHE_UPDATE", False) and indices.numel() > 0:
+        elif count_local and getattr(_engine, "FUSED_CACHE_UPDATE", False) and indices.numel() > 0:
             # frequency update folded into the preprocessing launch (same order as the reference:
             # count the batch's indices, then look them up)
             indices, rowidx, tableidx, n_tt, cache_locations = _engine.preprocess_indices_sync(
                 indices, offsets, self.num_tables, self.warmup, self.hashtbl, self.cache_state, self.cache_freq)
         else:
-            self.update_cache(indices)
+            if count_local:
+                self.update_cache(indices)
             indices, rowidx, tableidx, n_tt, cache_locations = _engine.preprocess_indices_sync(
                 indices, offsets, self.num_tables, self.warmup, self.hashtbl, self.cache_state)
         n_cached = indices.numel() - n_tt

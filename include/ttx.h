@@ -608,6 +608,54 @@ int ttx_cache_populate_f(const ttx_geom* g, const float* const* tt_cores,
                          void* workspace, size_t workspace_bytes,
                          ttx_stream_t stream);
 
+/* ------------------------------ row cache over several tables (not in the reference) -----
+ * The reference's cache serves one table (tt_embeddings_ops.py:456), and so do the entry points above.  For the num_tables
+ * tables of ONE row shape of a table-batched bag (no p_tables) a single hashtbl / cache_freq / cache_state / cache_weight set is
+ * keyed by
+ *
+ *   key = table * key_stride + index,   key_stride = prod(p) (>= num_embeddings: the range the index decode covers)
+ *
+ * so that the cache_size hottest rows ACROSS the tables are cached.  Every cache entry point above then works unchanged on
+ * keys in place of indices and on the output / gradient viewed as [num_tables * B, D] (bags addressed by their flat row
+ * table * B + b): ttx_update_cache_state, ttx_preprocess_indices_async called with num_tables = 1 and nb = num_tables * B
+ * bags (its part_rowidx is then the flat bag row), ttx_cache_forward_n, ttx_cache_backward_*_n, ttx_cache_backward_sorted.
+ * These three calls carry (table, index) into and out of key space and fill the cache rows:
+ *
+ *   ttx_table_keys        keys[n] = indices[n] + t(n) * key_stride, t(n) = the table whose extent
+ *                         [offsets[t B], offsets[(t + 1) B]) holds position n.  offsets: the batch's num_tables * B + 1 bag
+ *                         offsets, table-major, offsets[0] = 0 and the closing entry = nnz as everywhere; tables without
+ *                         lookups (equal boundaries) and empty bags are legal; t(n) always lies in [0, num_tables - 1].  With
+ *                         upd_hashtbl / upd_cache_freq (both or neither; H slots) the launch also counts the keys, exactly as
+ *                         ttx_update_cache_state would.  One thread per lookup searches the num_tables + 1 table boundaries
+ *                         (staged in LDS up to 1024 of them, read from the offsets beyond: no cap on num_tables), 64-bit
+ *                         arithmetic throughout (key_stride may exceed 2^32).  One launch, one writer per element.
+ *   ttx_table_keys_split  the inverse on the first *n_dev entries (a device int32, clamped to [0, n]; NULL: all n).
+ *                         bagrow != NULL (the part_rowidx of the live preprocess, flat bag rows): t = bagrow[s] / B,
+ *                         out_rowidx[s] = bagrow[s] - t B, out_indices[s] = keys[s] - t key_stride, out_tableidx[s] = t --
+ *                         what ttx_plan_build_n takes for the misses.  bagrow == NULL: t = keys[s] / key_stride and
+ *                         out_rowidx is not written (may be NULL).  t is clamped to [0, num_tables - 1] before it scales
+ *                         anything.  Entries at and beyond the count are NOT written (a counted plan does not read them).
+ *   ttx_cache_populate_t  ttx_cache_populate_f for a geometry with num_tables >= 1: the same sort and mark on the keys, the
+ *                         cache_size selected keys split (bagrow == NULL) and decompressed by ttx_tt_rows with their
+ *                         tables; an empty slot among them is row 0 of table 0.  key_stride <= prod(p).  Honours
+ *                         TTX_POPULATE_REFERENCE_EXACT.  One 8-byte read-back sizes the sort, as in ttx_cache_populate.
+ *   nnz == 0 / n == 0     returns 0 and launches nothing.
+ *   errors                a negative size, nnz >= 2^31, B <= 0, num_tables <= 0, key_stride <= 0, num_tables * B >= 2^31,
+ *                         num_tables * key_stride >= 2^62, counting with one of the two tables missing or H outside
+ *                         (0, 2^31), an int64 pointer not 8-byte (n_dev: 4-byte) aligned, a NULL pointer that would be read
+ *                         or written: -1 with ttx_last_error() set, before anything touches a device.
+ * Nothing is read back by the first two (capturable); no atomics except the frequency count's. */
+int ttx_table_keys(int64_t nnz, const int64_t* indices, int32_t num_tables, int64_t B, const int64_t* offsets,
+                   int64_t key_stride, int64_t* keys, int64_t H, int64_t* upd_hashtbl, int64_t* upd_cache_freq,
+                   ttx_stream_t stream);
+int ttx_table_keys_split(int64_t n, const int32_t* n_dev, int32_t num_tables, int64_t B, int64_t key_stride,
+                         const int64_t* keys, const int64_t* bagrow, int64_t* out_indices, int64_t* out_tableidx,
+                         int64_t* out_rowidx, ttx_stream_t stream);
+size_t ttx_cache_populate_t_workspace_bytes(const ttx_geom* g, int64_t hashtbl_size, int64_t cache_size, int32_t D);
+int ttx_cache_populate_t(const ttx_geom* g, const float* const* tt_cores, int64_t hashtbl_size, int64_t* hashtbl,
+                         int64_t* cache_freq, int32_t* cache_state, int64_t cache_size, int32_t D, float* cache_weight,
+                         int64_t key_stride, int32_t flags, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
+
 /* replaces cache_forward_cuda (tt_embeddings.cpp:97-103,
  * tt_embeddings_cuda.cu:1498-1572): output[rowidx[n], :] += cache_weight[
  * cache_locations[n], :], summed per run of equal rowidx. */
