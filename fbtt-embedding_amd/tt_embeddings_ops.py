@@ -274,10 +274,102 @@ def tt_matrix_to_full(tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: 
     return full if full.dtype == torch.float64 else full.float()  # (float64 cores: a float64 table, for the tests' references)
 
 
+# --------------------------------------------------------------------------- #
+# what the lookup nodes below share: the optimizer dispatch of the cores' and the cache rows' update, and the gradient tuple
+# --------------------------------------------------------------------------- #
+
+def _optim_code(sparse: bool, optimizer: OptimType) -> Tuple[bool, int]:
+    """-> (use_state, optim): whether the optimizer keeps a state (Adagrad), and the C++ node's code of the update
+    (0 fused SGD, 1 fused Adagrad, 2 dense gradients)."""
+    use_state = sparse and optimizer not in _SGD_LIKE
+    return use_state, 2 if not sparse else (1 if use_state else 0)
+
+
+def _num_tables(tt_p_shapes, tt_cores) -> int:
+    if len(tt_p_shapes) > 0 and isinstance(tt_p_shapes[0], (list, tuple)):
+        return len(tt_p_shapes)  # tables of different row factors: cores are [1, sum p, slice]
+    return tt_cores[0].size(0)
+
+
+def _stash(ctx, D: int, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer: OptimType, learning_rate: float, eps: float, sparse: bool,
+           optimizer_state, tt_cores) -> None:
+    """what the update helpers below read off a node's ctx"""
+    ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
+    ctx.D = D
+    ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
+    ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+
+
+def _update_cores_rows(ctx, D: int, nnz: int, indices, tableidx, d_rows) -> Optional[List[torch.Tensor]]:
+    """The cores' update from one gradient row per lookup, on ctx.plan: fused SGD / Adagrad in place (-> None), or the dense
+    core gradients."""
+    p, q, ranks = ctx.geometry
+    if not ctx.sparse:
+        optim, lr, eps, state = _engine.OPTIM_DENSE, 0.0, 0.0, None
+    elif ctx.optimizer in _SGD_LIKE:
+        optim, lr, eps, state = _engine.OPTIM_SGD, ctx.learning_rate, 0.0, None
+    else:
+        optim, lr, eps, state = _engine.OPTIM_ADAGRAD, ctx.learning_rate, ctx.eps, list(ctx.optimizer_state)
+    return _engine.tt_backward_rows(optim, D, lr, eps, p, q, ranks, nnz, indices, tableidx, d_rows, list(ctx.tt_cores), state,
+                                    ctx.plan)
+
+
+def _update_cores_bags(ctx, L, nnz: int, indices, rowidx, tableidx, d_output) -> Optional[List[torch.Tensor]]:
+    """The cores' update from the bags' gradient (the reference's three entry points), on ctx.plan when there is one (the
+    tests' CPU engine takes no such keyword): fused SGD / Adagrad in place (-> None), or the dense core gradients."""
+    p, q, ranks = ctx.geometry
+    extra = {"plan": ctx.plan} if ctx.plan is not None else {}
+    cores = list(ctx.tt_cores)
+    if not ctx.sparse:
+        return _engine.tt_dense_backward(1000, ctx.D, p, q, ranks, L, nnz, indices, rowidx, tableidx, d_output, cores, **extra)
+    if ctx.optimizer in _SGD_LIKE:
+        _engine.tt_sgd_backward(1000, ctx.D, ctx.learning_rate, p, q, ranks, L, nnz, indices, rowidx, tableidx, d_output, cores,
+                                **extra)
+    else:
+        _engine.tt_adagrad_backward(1000, ctx.D, ctx.learning_rate, ctx.eps, p, q, ranks, L, nnz, indices, rowidx, tableidx,
+                                    d_output, ctx.optimizer_state, cores, **extra)
+    return None
+
+
+def _update_cache_rows(ctx, det: Optional[bool], batch: int, nnz: int, d_output, cache_locations, rowidx, cache_optimizer_state,
+                       cache_weight, skip_dev: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The cache rows' update: SGD / row-wise Adagrad in place (-> None), or the dense gradient of cache_weight.  `det` is the
+    module's deterministic_cache_update; None ("auto") looks at the BATCH (`batch` = misses + hits), as the C++ node does
+    (csrc/ttx_torch.cpp kSortedAutoNnz: its split point stays on the device): all routes switch at the same batch size.  The
+    engine's own default would look at the cached part alone.  The two keywords are passed only when set (None is their
+    default; the tests' CPU engine takes neither)."""
+    adagrad, _ = _optim_code(ctx.sparse, ctx.optimizer)
+    auto = getattr(_engine, "_use_sorted", None)
+    if det is None and auto is not None:
+        det = auto(None, batch, adagrad=adagrad)
+    kw = {} if det is None else {"deterministic": det}
+    if skip_dev is not None:
+        kw["skip_dev"] = skip_dev
+    if not ctx.sparse:
+        return _engine.cache_backward_dense(nnz, d_output, cache_locations, rowidx, ctx.learning_rate, cache_weight, **kw)
+    if adagrad:
+        _engine.cache_backward_rowwise_adagrad_approx(nnz, d_output, cache_locations, rowidx, ctx.learning_rate, ctx.eps,
+                                                      cache_optimizer_state, cache_weight, **kw)
+    else:
+        _engine.cache_backward_sgd(nnz, d_output, cache_locations, rowidx, ctx.learning_rate, cache_weight, **kw)
+    return None
+
+
+def _grad_tuple(node, n_cores: int, core_grads=None, d_cache_weight: Optional[torch.Tensor] = None) -> tuple:
+    """backward's result for `node`: None for each of its N_ARGS non-core arguments -- but for `d_cache_weight`, where there is
+    one, at CACHE_WEIGHT_ARG --, then one entry per core (None under a fused optimizer)."""
+    head: List[Optional[torch.Tensor]] = [None] * node.N_ARGS
+    if d_cache_weight is not None:
+        head[node.CACHE_WEIGHT_ARG] = d_cache_weight
+    return tuple(head + (list(core_grads) if core_grads is not None else [None] * n_cores))
+
+
 class TTLookupFunction(torch.autograd.Function):
     """Autograd node of one (table-batched) TT lookup.  Argument order and the
     gradient tuple (19 x None, `d_cache_weight` in slot 17 for dense mode, then
     one entry per core) follow the reference (:133-155, :280-356)."""
+
+    N_ARGS, CACHE_WEIGHT_ARG = 19, 17  # (of forward's arguments after ctx, in front of the cores)
 
     @staticmethod
     def forward(ctx, B: int, D: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
@@ -286,17 +378,11 @@ class TTLookupFunction(torch.autograd.Function):
                 cache_locations: Optional[torch.Tensor], cache_optimizer_state: Optional[torch.Tensor],
                 cache_weight: Optional[torch.Tensor], optimizer_state: List[torch.Tensor],
                 *tt_cores: torch.Tensor) -> torch.Tensor:
-        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
-        ctx.D = D
-        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
-        ctx.tt_cores = tt_cores
-        ctx.optimizer_state = optimizer_state
+        _stash(ctx, D, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer, learning_rate, eps, sparse, optimizer_state, tt_cores)
         ctx.nnz_tt, ctx.nnz_cached = nnz_tt, nnz_cached
         ctx.has_cache = cache_weight is not None
         ctx.save_for_backward(L, indices, rowidx, tableidx, cache_locations, cache_optimizer_state, cache_weight)
-        num_tables = tt_cores[0].size(0)
-        if len(tt_p_shapes) > 0 and isinstance(tt_p_shapes[0], (list, tuple)):
-            num_tables = len(tt_p_shapes)  # tables of different row factors: cores are [1, sum p, slice]
+        num_tables = _num_tables(tt_p_shapes, tt_cores)
         # one lookup plan serves forward and backward of this batch
         mk = getattr(_engine, "make_plan", None)
         ctx.plan = getattr(rowidx, "_ttx_plan", None)  # built by the module's lookup prologue
@@ -313,40 +399,14 @@ class TTLookupFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         L, indices, rowidx, tableidx, cache_locations, cache_optimizer_state, cache_weight = ctx.saved_tensors
-        p, q, ranks = ctx.geometry
         n_tt, n_c = ctx.nnz_tt, ctx.nnz_cached
-        extra = {"plan": ctx.plan} if ctx.plan is not None else {}
-        det_flag = ctx.det
-        auto = getattr(_engine, "_use_sorted", None)
-        if det_flag is None and n_c > 0 and auto is not None:
-            # "auto" looks at the BATCH (misses + hits), as the C++ node does (csrc/ttx_torch.cpp kSortedAutoNnz: its split point
-            # stays on the device): both routes switch at the same batch size.  The engine's own default would look at n_c alone.
-            det_flag = auto(None, n_tt + n_c, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
-        det = {"deterministic": det_flag} if det_flag is not None else {}
-        cores = list(ctx.tt_cores)
         d_output = d_output.contiguous()
-        head: List[Optional[torch.Tensor]] = [None] * 19
-        if ctx.sparse:
-            if ctx.optimizer in _SGD_LIKE:
-                _engine.tt_sgd_backward(1000, ctx.D, ctx.learning_rate, p, q, ranks, L, n_tt, indices, rowidx, tableidx,
-                                        d_output, cores, **extra)
-                if n_c > 0:
-                    _engine.cache_backward_sgd(n_c, d_output, cache_locations[n_tt:], rowidx[n_tt:],
-                                               ctx.learning_rate, cache_weight, **det)
-            else:
-                _engine.tt_adagrad_backward(1000, ctx.D, ctx.learning_rate, ctx.eps, p, q, ranks, L, n_tt, indices,
-                                            rowidx, tableidx, d_output, ctx.optimizer_state, cores, **extra)
-                if n_c > 0:
-                    _engine.cache_backward_rowwise_adagrad_approx(n_c, d_output, cache_locations[n_tt:],
-                                                                  rowidx[n_tt:], ctx.learning_rate, ctx.eps,
-                                                                  cache_optimizer_state, cache_weight, **det)
-            return tuple(head + [None] * len(cores))
-        grads = _engine.tt_dense_backward(1000, ctx.D, p, q, ranks, L, n_tt, indices, rowidx, tableidx, d_output,
-                                          cores, **extra)
+        grads = _update_cores_bags(ctx, L, n_tt, indices, rowidx, tableidx, d_output)
+        d_cache_weight = None
         if n_c > 0:
-            head[17] = _engine.cache_backward_dense(n_c, d_output, cache_locations[n_tt:], rowidx[n_tt:],
-                                                    ctx.learning_rate, cache_weight, **det)
-        return tuple(head + list(grads))
+            d_cache_weight = _update_cache_rows(ctx, ctx.det, n_tt + n_c, n_c, d_output, cache_locations[n_tt:], rowidx[n_tt:],
+                                                cache_optimizer_state, cache_weight)
+        return _grad_tuple(TTLookupFunction, len(ctx.tt_cores), grads, d_cache_weight)
 
 
 # --------------------------------------------------------------------------- #
@@ -391,13 +451,13 @@ class TTMaxLookupFunction(torch.autograd.Function):
     winning lookup's row only (a gradient row per lookup), and the ordinary backward / fused optimizer runs on those rows.  The
     lookup plan is built without bag rows, so that forward and backward share it (four cores: the merged last cores too)."""
 
+    N_ARGS = 12
+
     @staticmethod
     def forward(ctx, B: int, D: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
                 indices: torch.Tensor, offsets: torch.Tensor, optimizer: OptimType, learning_rate: float, eps: float,
                 sparse: bool, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
-        num_tables = tt_cores[0].size(0)
-        if len(tt_p_shapes) > 0 and isinstance(tt_p_shapes[0], (list, tuple)):
-            num_tables = len(tt_p_shapes)  # tables of different row factors: cores are [1, sum p, slice]
+        num_tables = _num_tables(tt_p_shapes, tt_cores)
         nnz = indices.numel()
         no_cache = indices.new_empty(0)
         _, rowidx, tableidx, _, _ = _engine.preprocess_indices_sync(indices, offsets, num_tables, True, no_cache,
@@ -405,32 +465,17 @@ class TTMaxLookupFunction(torch.autograd.Function):
         plan = _engine.make_plan(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, nnz, indices, tableidx)  # (no bag rows)
         rows = _engine.tt_rows_p(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, list(tt_cores), plan)
         out, argmax = _engine.bag_max_pool(rows, offsets)
-        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
-        ctx.D, ctx.nnz, ctx.plan = D, nnz, plan
-        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
-        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        _stash(ctx, D, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer, learning_rate, eps, sparse, optimizer_state, tt_cores)
+        ctx.nnz, ctx.plan = nnz, plan
         ctx.save_for_backward(indices, offsets, tableidx, argmax)
         return out.view(num_tables, B, D)
 
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         indices, offsets, tableidx, argmax = ctx.saved_tensors
-        p, q, ranks = ctx.geometry
-        cores = list(ctx.tt_cores)
         d_rows = _engine.bag_max_pool_backward(d_output.contiguous(), argmax, offsets, ctx.nnz)
-        head: List[Optional[torch.Tensor]] = [None] * 12
-        if ctx.sparse:
-            if ctx.optimizer in _SGD_LIKE:
-                _engine.tt_backward_rows(_engine.OPTIM_SGD, ctx.D, ctx.learning_rate, 0.0, p, q, ranks, ctx.nnz, indices,
-                                         tableidx, d_rows, cores, None, ctx.plan)
-            else:
-                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, ctx.D, ctx.learning_rate, ctx.eps, p, q, ranks, ctx.nnz, indices,
-                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
-            return tuple(head + [None] * len(cores))
-        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, ctx.D, 0.0, 0.0, p, q, ranks, ctx.nnz, indices, tableidx, d_rows,
-                                         cores, None, ctx.plan)
-        return tuple(head + list(grads))
-
+        grads = _update_cores_rows(ctx, ctx.D, ctx.nnz, indices, tableidx, d_rows)
+        return _grad_tuple(TTMaxLookupFunction, len(ctx.tt_cores), grads)
 
 
 class TTRowsLookupFunction(torch.autograd.Function):
@@ -442,16 +487,16 @@ class TTRowsLookupFunction(torch.autograd.Function):
     compacted order and the positions.  `parts` = k > 1: the geometry handed in is the core-0 row split's, `indices` hold the k
     part lookups of every position and a rows buffer [N, D] IS the parts' [k N, D / k].  Nothing is read back."""
 
+    N_ARGS = 14
+
     @staticmethod
     def forward(ctx, N: int, D: int, parts: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
                 indices: torch.Tensor, rank: Optional[torch.Tensor], n_dev: Optional[torch.Tensor], optimizer: OptimType,
                 learning_rate: float, eps: float, sparse: bool, optimizer_state: List[torch.Tensor],
                 *tt_cores: torch.Tensor) -> torch.Tensor:
         k = max(1, parts)
-        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
-        ctx.N, ctx.D, ctx.k = N, D, k
-        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
-        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        _stash(ctx, D, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer, learning_rate, eps, sparse, optimizer_state, tt_cores)
+        ctx.N, ctx.k = N, k
         if N == 0:
             ctx.plan = None
             return tt_cores[0].new_empty((0, D))
@@ -465,28 +510,16 @@ class TTRowsLookupFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
-        cores = list(ctx.tt_cores)
-        head: List[Optional[torch.Tensor]] = [None] * 14
+        cores = ctx.tt_cores
         if ctx.N == 0:  # an empty batch: nothing to train, zero dense gradients
-            return tuple(head + [None if ctx.sparse else torch.zeros_like(c) for c in cores])
+            return _grad_tuple(TTRowsLookupFunction, len(cores), None if ctx.sparse else [torch.zeros_like(c) for c in cores])
         indices, tableidx, rank = ctx.saved_tensors
-        p, q, ranks = ctx.geometry
         N, D, k = ctx.N, ctx.D, ctx.k
         d_rows = d_output.contiguous().view(N, D)
         if rank is not None:
             d_rows = _engine.rows_collect(rank, d_rows)
-        d_rows = d_rows.view(k * N, D // k)
-        if ctx.sparse:
-            if ctx.optimizer in _SGD_LIKE:
-                _engine.tt_backward_rows(_engine.OPTIM_SGD, D // k, ctx.learning_rate, 0.0, p, q, ranks, k * N, indices, tableidx,
-                                         d_rows, cores, None, ctx.plan)
-            else:
-                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, D // k, ctx.learning_rate, ctx.eps, p, q, ranks, k * N, indices,
-                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
-            return tuple(head + [None] * len(cores))
-        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, D // k, 0.0, 0.0, p, q, ranks, k * N, indices, tableidx, d_rows,
-                                         cores, None, ctx.plan)
-        return tuple(head + list(grads))
+        grads = _update_cores_rows(ctx, D // k, k * N, indices, tableidx, d_rows.view(k * N, D // k))
+        return _grad_tuple(TTRowsLookupFunction, len(cores), grads)
 
 
 class TTRowsCachedLookupFunction(torch.autograd.Function):
@@ -504,6 +537,8 @@ class TTRowsCachedLookupFunction(torch.autograd.Function):
     misses', a plan count computed on the device), and the rows [n, D] ARE the parts' [k n, D / k].
     Nothing is read back."""
 
+    N_ARGS, CACHE_WEIGHT_ARG = 21, 19
+
     @staticmethod
     def forward(ctx, N: int, D: int, parts: int, tt_p_shapes: List[int], tt_q_shapes: List[int], tt_ranks: List[int],
                 indices: torch.Tensor, offsets: torch.Tensor, rank: Optional[torch.Tensor], unit_offsets: Optional[torch.Tensor],
@@ -513,10 +548,8 @@ class TTRowsCachedLookupFunction(torch.autograd.Function):
                 cache_weight: torch.Tensor, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
         k = max(1, parts)
         n = indices.numel()
-        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
-        ctx.N, ctx.n, ctx.D, ctx.k, ctx.det = N, n, D, k, det
-        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
-        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        _stash(ctx, D, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer, learning_rate, eps, sparse, optimizer_state, tt_cores)
+        ctx.N, ctx.n, ctx.k, ctx.det = N, n, k, det
         pcol, prow, ploc, n_tt = _engine.preprocess_indices_async(indices, offsets, hashtbl, cache_state, cache_freq)
         lookups, n_dev = pcol, n_tt
         if k > 1:
@@ -533,32 +566,12 @@ class TTRowsCachedLookupFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         lookups, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight = ctx.saved_tensors
-        p, q, ranks = ctx.geometry
         N, n, D, k = ctx.N, ctx.n, ctx.D, ctx.k
-        cores = list(ctx.tt_cores)
-        head: List[Optional[torch.Tensor]] = [None] * 21
         d_out = d_output.contiguous().view(N, D)
         d_rows = _engine.rows_pick(n_tt, prow, d_out)[:n].view(k * n, D // k)
-        det = ctx.det
-        auto = getattr(_engine, "_use_sorted", None)
-        if det is None and auto is not None:  # "auto" looks at the BATCH (misses + hits), as TTLookupFunction.backward does
-            det = auto(None, n, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
-        if ctx.sparse:
-            if ctx.optimizer in _SGD_LIKE:
-                _engine.tt_backward_rows(_engine.OPTIM_SGD, D // k, ctx.learning_rate, 0.0, p, q, ranks, k * n, lookups, tableidx,
-                                         d_rows, cores, None, ctx.plan)
-                _engine.cache_backward_sgd(n, d_out, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det, skip_dev=n_tt)
-            else:
-                _engine.tt_backward_rows(_engine.OPTIM_ADAGRAD, D // k, ctx.learning_rate, ctx.eps, p, q, ranks, k * n, lookups,
-                                         tableidx, d_rows, cores, list(ctx.optimizer_state), ctx.plan)
-                _engine.cache_backward_rowwise_adagrad_approx(n, d_out, ploc, prow, ctx.learning_rate, ctx.eps,
-                                                              cache_optimizer_state, cache_weight, deterministic=det, skip_dev=n_tt)
-            return tuple(head + [None] * len(cores))
-        grads = _engine.tt_backward_rows(_engine.OPTIM_DENSE, D // k, 0.0, 0.0, p, q, ranks, k * n, lookups, tableidx, d_rows,
-                                         cores, None, ctx.plan)
-        head[19] = _engine.cache_backward_dense(n, d_out, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det,
-                                                skip_dev=n_tt)
-        return tuple(head + list(grads))
+        grads = _update_cores_rows(ctx, D // k, k * n, lookups, tableidx, d_rows)
+        d_cache_weight = _update_cache_rows(ctx, ctx.det, n, n, d_out, ploc, prow, cache_optimizer_state, cache_weight, skip_dev=n_tt)
+        return _grad_tuple(TTRowsCachedLookupFunction, len(ctx.tt_cores), grads, d_cache_weight)
 
 
 class TTTablesCachedLookupFunction(torch.autograd.Function):
@@ -572,6 +585,8 @@ class TTTablesCachedLookupFunction(torch.autograd.Function):
     Adagrad or dense backward on the plan, and the cache rows' update with rowidx = the flat bag rows and skip_dev = the split
     point: SGD, row-wise Adagrad, or the dense gradient of cache_weight (returned in its slot).  Nothing is read back."""
 
+    N_ARGS, CACHE_WEIGHT_ARG = 21, 19
+
     @staticmethod
     def forward(ctx, B: int, D: int, num_tables: int, key_stride: int, tt_p_shapes: List[int], tt_q_shapes: List[int],
                 tt_ranks: List[int], L: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor, hashtbl: torch.Tensor,
@@ -579,10 +594,8 @@ class TTTablesCachedLookupFunction(torch.autograd.Function):
                 learning_rate: float, eps: float, sparse: bool, cache_optimizer_state: Optional[torch.Tensor],
                 cache_weight: torch.Tensor, optimizer_state: List[torch.Tensor], *tt_cores: torch.Tensor) -> torch.Tensor:
         n = indices.numel()
-        ctx.geometry = (tt_p_shapes, tt_q_shapes, tt_ranks)
-        ctx.B, ctx.D, ctx.nt, ctx.n, ctx.det = B, D, num_tables, n, det
-        ctx.optimizer, ctx.learning_rate, ctx.eps, ctx.sparse = optimizer, learning_rate, eps, sparse
-        ctx.tt_cores, ctx.optimizer_state = tt_cores, optimizer_state
+        _stash(ctx, D, tt_p_shapes, tt_q_shapes, tt_ranks, optimizer, learning_rate, eps, sparse, optimizer_state, tt_cores)
+        ctx.B, ctx.nt, ctx.n, ctx.det = B, num_tables, n, det
         keys = _engine.table_keys(indices, offsets, num_tables, key_stride)
         pkey, prow, ploc, n_tt = _engine.preprocess_indices_async(keys, offsets, hashtbl, cache_state, cache_freq)
         # (prow: the flat bag row table * B + b -- the preprocess saw one table of num_tables * B bags)
@@ -598,31 +611,12 @@ class TTTablesCachedLookupFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         L, idx, rowidx, tableidx, prow, ploc, n_tt, cache_optimizer_state, cache_weight = ctx.saved_tensors
-        p, q, ranks = ctx.geometry
-        n, D = ctx.n, ctx.D
-        cores = list(ctx.tt_cores)
-        head: List[Optional[torch.Tensor]] = [None] * 21
+        n = ctx.n
         d_output = d_output.contiguous()
-        d_flat = d_output.view(ctx.nt * ctx.B, D)
-        det = ctx.det
-        auto = getattr(_engine, "_use_sorted", None)
-        if det is None and auto is not None:  # "auto" looks at the BATCH (misses + hits), as TTLookupFunction.backward does
-            det = auto(None, n, adagrad=ctx.sparse and ctx.optimizer not in _SGD_LIKE)
-        if ctx.sparse:
-            if ctx.optimizer in _SGD_LIKE:
-                _engine.tt_sgd_backward(1000, D, ctx.learning_rate, p, q, ranks, L, n, idx, rowidx, tableidx, d_output, cores,
-                                        plan=ctx.plan)
-                _engine.cache_backward_sgd(n, d_flat, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det, skip_dev=n_tt)
-            else:
-                _engine.tt_adagrad_backward(1000, D, ctx.learning_rate, ctx.eps, p, q, ranks, L, n, idx, rowidx, tableidx,
-                                            d_output, ctx.optimizer_state, cores, plan=ctx.plan)
-                _engine.cache_backward_rowwise_adagrad_approx(n, d_flat, ploc, prow, ctx.learning_rate, ctx.eps,
-                                                              cache_optimizer_state, cache_weight, deterministic=det, skip_dev=n_tt)
-            return tuple(head + [None] * len(cores))
-        grads = _engine.tt_dense_backward(1000, D, p, q, ranks, L, n, idx, rowidx, tableidx, d_output, cores, plan=ctx.plan)
-        head[19] = _engine.cache_backward_dense(n, d_flat, ploc, prow, ctx.learning_rate, cache_weight, deterministic=det,
-                                                skip_dev=n_tt)
-        return tuple(head + list(grads))
+        d_flat = d_output.view(ctx.nt * ctx.B, ctx.D)
+        grads = _update_cores_bags(ctx, L, n, idx, rowidx, tableidx, d_output)
+        d_cache_weight = _update_cache_rows(ctx, ctx.det, n, n, d_flat, ploc, prow, cache_optimizer_state, cache_weight, skip_dev=n_tt)
+        return _grad_tuple(TTTablesCachedLookupFunction, len(ctx.tt_cores), grads, d_cache_weight)
 
 
 class _RowsAtPositionsFunction(torch.autograd.Function):
@@ -1215,8 +1209,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     def _forward_split0(self, fast, indices: torch.Tensor, offsets: torch.Tensor, k: int) -> torch.Tensor:
         """q0 = k q0': k part lookups per index through the C++ node on the table [k p0, p1, p2] x [q0', q1, q2] (views of
         core 0 and its optimizer state: the same memory); the output [tables, k B, D / k] IS [tables, B, D]."""
-        use_state = self.sparse and self.optimizer not in _SGD_LIKE
-        optim = 2 if not self.sparse else (1 if use_state else 0)
+        use_state, optim = _optim_code(self.sparse, self.optimizer)
         if self.use_cache and self.num_tables == 1:  # (the frequency table counts the caller's indices, not the part lookups;
             _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)  # several tables: _forward_sum counted their keys)
         p, q, nt = self.tt_p_shapes, self.tt_q_shapes, self.num_tables
@@ -1289,8 +1282,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         offsets = offsets.long() if offsets.dtype != torch.int64 else offsets
         indices = indices if indices.is_contiguous() else indices.contiguous()
         offsets = offsets if offsets.is_contiguous() else offsets.contiguous()
-        use_state = self.sparse and self.optimizer not in _SGD_LIKE
-        optim = 2 if not self.sparse else (1 if use_state else 0)
+        use_state, optim = _optim_code(self.sparse, self.optimizer)
         p_flat = getattr(self, "_p_flat", self.tt_p_shapes)
         pre = fast.prologue(indices, offsets, self.num_tables, p_flat, self.tt_q_shapes, self.tt_ranks, None, None,
                             n_dev.to(torch.int32).reshape(1))
@@ -1499,7 +1491,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                     raise NotImplementedError("a live row cache over several tables serves GPU tensors only")
                 if per_sample_weights is not None:
                     raise NotImplementedError("per_sample_weights with a live row cache over several tables")
-                use_state = self.sparse and self.optimizer not in _SGD_LIKE
+                use_state, _ = _optim_code(self.sparse, self.optimizer)
                 return TTTablesCachedLookupFunction.apply(
                     (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.num_tables, self._key_stride(),
                     self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, self.L, indices.contiguous(), offsets.contiguous(),
@@ -1720,6 +1712,14 @@ class TTEmbedding(TTEmbeddingBag):
             p, q = [k * p[0], p[1], p[2]], [q[0] // k, q[1], q[2]]
         return k, p, q, cores, state
 
+    def _no_live_rows(self, flat: torch.Tensor, N: int) -> torch.Tensor:
+        """no live lookup (an empty batch, or N positions of padding only) -> [N, D] zeros through the empty lookup's node, whose
+        backward trains nothing and gives zero dense gradients"""
+        out = TTRowsLookupFunction.apply(0, self.embedding_dim, 1, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat[:0], None,
+                                         None, self.optimizer, self.learning_rate, self.eps, self.sparse,
+                                         list(self.optimizer_state), *self.tt_cores)
+        return out if N == 0 else torch.zeros((N, self.embedding_dim), dtype=torch.float32, device=flat.device) + out.sum()
+
     def _forward_cached(self, flat: torch.Tensor, N: int, pad: Optional[int], use_state: bool) -> torch.Tensor:
         """GPU tensors, the cache live -> [N, D] (TTRowsCachedLookupFunction).  Without padding_idx nothing is read back; with it
         the live count is (it sizes the partition), as in the bag module."""
@@ -1732,10 +1732,7 @@ class TTEmbedding(TTEmbeddingBag):
             flat, rank, n_live = _engine.bags_compact(flat, None, 1, pad)
             n = int(n_live.item())
             if n == 0:  # padding only: zeros, nothing trained, nothing counted (zero dense gradients, as an empty batch gives)
-                out = TTRowsLookupFunction.apply(0, D, 1, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat[:0], None, None,
-                                                 self.optimizer, self.learning_rate, self.eps, self.sparse,
-                                                 list(self.optimizer_state), *self.tt_cores)
-                return torch.zeros((N, D), dtype=torch.float32, device=dev) + out.sum()
+                return self._no_live_rows(flat, N)
             flat = flat[:n]
         k, p, q, cores, state = self._split_geometry(use_state)
         unit = self._fixed_offsets(dev, n, 1)
@@ -1753,12 +1750,9 @@ class TTEmbedding(TTEmbeddingBag):
         flat = flat if flat.is_contiguous() else flat.contiguous()
         N = flat.numel()
         pad = self.__dict__.get("padding_idx")
-        use_state = self.sparse and self.optimizer not in _SGD_LIKE
-        p, q, ranks = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks
+        use_state, _ = _optim_code(self.sparse, self.optimizer)
         if N == 0:
-            out = TTRowsLookupFunction.apply(0, D, 1, p, q, ranks, flat, None, None, self.optimizer, self.learning_rate, self.eps,
-                                             self.sparse, list(self.optimizer_state), *self.tt_cores)
-            return out.view(shape + (D,))
+            return self._no_live_rows(flat, 0).view(shape + (D,))
         if not flat.is_cuda:
             # the tests' oracle engine: the bag module's reference-shaped route with one bag per live position, the padding
             # dropped (and the rows put back) with torch ops
@@ -1785,9 +1779,7 @@ class TTEmbedding(TTEmbeddingBag):
             live, rank, n_live = _engine.bags_compact(flat, None, 1, pad)
             n = int(n_live.item())
             if n == 0:
-                out = TTRowsLookupFunction.apply(0, D, 1, p, q, ranks, flat[:0], None, None, self.optimizer, self.learning_rate,
-                                                 self.eps, self.sparse, list(self.optimizer_state), *self.tt_cores)
-                return (torch.zeros((N, D), dtype=torch.float32, device=flat.device) + out.sum()).view(shape + (D,))
+                return self._no_live_rows(flat, N).view(shape + (D,))
             return _RowsAtPositionsFunction.apply(self._bag_rows(live[:n].contiguous()), rank).view(shape + (D,))
         rank = n_dev = None
         if pad is not None:
@@ -1809,6 +1801,6 @@ class TTEmbedding(TTEmbeddingBag):
             flat, _ = _engine.split0_expand(flat, self._fixed_offsets(flat.device, N, 1), k, p[1] * p[2])
             if n_dev is not None:
                 n_dev = n_dev * k
-        out = TTRowsLookupFunction.apply(N, D, k, p, q, ranks, flat, rank, n_dev, self.optimizer, self.learning_rate, self.eps,
+        out = TTRowsLookupFunction.apply(N, D, k, p, q, self.tt_ranks, flat, rank, n_dev, self.optimizer, self.learning_rate, self.eps,
                                          self.sparse, state, *cores)
         return out.view(shape + (D,))
