@@ -118,7 +118,17 @@ struct Plan {
   float* t4m;   // [position][r2 q2 q3]
   float* t4g;   // [lookup n][r2 q2 q3]
   int4* t4o;    // [position in core 2's sorted order] = {lookup n, sid_2, sid_3, row of its core-3 partial (ipos[3][n])}
+  int cols;     // columns of the pivot's dispatch order (chunk_dispatch_index, ttx_plan.hip): g_chunk_cols when the plan was carved
 };
+
+// Columns over which the one-launch and wide plan routes deal the pivot's chunk slots: the 8 XCDs that consecutive work-groups
+// go round.  A/B knob of the test build (ttx_debug_skip bit 17 -> 1 column: the list in slot order), defined in ttx_plan.hip.
+constexpr int kChunkCols = 8;
+#ifdef TTX_TEST_HOOKS
+extern int g_chunk_cols;
+#else
+constexpr int g_chunk_cols = kChunkCols;
+#endif
 
 int choose_chunk(const Dims& d, long long nnz);  // lookups per chunk (kernel variant / LDS-budget heuristic)
 // floats of per-lookup scratch a four-core geometry needs in its plan to run on the three-core kernels (0: it does not)

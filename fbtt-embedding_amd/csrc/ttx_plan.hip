@@ -42,6 +42,7 @@ constexpr int kPlanWaves = kPlanThreads / kWave;
 #ifdef TTX_TEST_HOOKS
 static int g_plan_route = 0;
 #define TTX_PLAN_ROUTE(id) (g_plan_route = (id))
+int g_chunk_cols = kChunkCols;  // (ttx_internal.h; ttx_debug_skip bit 17 sets it to 1)
 #else
 #define TTX_PLAN_ROUTE(id) ((void)0)
 #endif
@@ -83,6 +84,7 @@ Plan carve_plan(const Dims& d, long long nnz, void* base) {
   memset(&P, 0, sizeof(P));
   P.MC = choose_chunk(d, nnz);
   P.max_chunks = max_chunks(d, nnz, P.MC);
+  P.cols = g_chunk_cols;
   int* cur = (int*)base;
   auto take = [&](size_t k) { int* r = cur; cur += r64(k); return r; };
   P.hdr = take(64);
@@ -479,6 +481,34 @@ __global__ __launch_bounds__(kMbThreads) void mb_count_kernel(
 template <typename T>
 __device__ __forceinline__ T* shifted(T* p, long long bytes) { return (T*)((char*)p + bytes); }
 
+// The pivot's DISPATCH order: the n chunk slots (slice-major) are cut into C segments of K or K + 1 consecutive slots
+// (K = n / C, the first n % C segments take the extra one) and segment r becomes column r of a row-major [rows][C]
+// list: slot start_r + k -> list index C k + r.  A bijection of [0, n); every residue mod C gets K or K + 1 chunks; a
+// slice's chunks share one residue (and sit in consecutive rows) unless the slice straddles one of the C - 1 segment
+// boundaries.  n < C and C = 1 give the identity.
+struct ChunkCols { int C, K, rem, head; };  // rem = n % C longer segments, head = rem (K + 1) slots in them
+__device__ __forceinline__ ChunkCols chunk_cols(int n, int C) {
+  const int K = n / C, rem = n - K * C;
+  return ChunkCols{C, K, rem, rem * (K + 1)};
+}
+__device__ __forceinline__ int chunk_dispatch_index(const ChunkCols& cc, int x) {
+  if (x < cc.head) return cc.C * (x % (cc.K + 1)) + x / (cc.K + 1);
+  const int y = x - cc.head;  // (K >= 1: with K == 0 every slot lies in the head)
+  return cc.C * (y % cc.K) + cc.rem + y / cc.K;
+}
+// the same along CONSECUTIVE slots without a division per slot: (column r, row k) of the first one, then one step per slot
+struct ChunkWalk { int r, k; };
+__device__ __forceinline__ ChunkWalk chunk_walk(const ChunkCols& cc, int x) {
+  if (x < cc.head) return ChunkWalk{x / (cc.K + 1), x % (cc.K + 1)};
+  const int y = x - cc.head;
+  return ChunkWalk{cc.rem + y / cc.K, y % cc.K};
+}
+__device__ __forceinline__ int chunk_walk_next(const ChunkCols& cc, ChunkWalk& w) {  // index of the slot at w; w moves on
+  const int idx = cc.C * w.k + w.r;
+  if (++w.k == cc.K + (w.r < cc.rem ? 1 : 0)) { w.k = 0; ++w.r; }
+  return idx;
+}
+
 // Single 8-bit pass (every S[t] <= 256): digit == slice id, so the digit prefix IS the slice
 // offset table and the pivot's chunk list follows from the digit totals -- what mb_finish would
 // recompute from the sorted keys.  One 256-thread work-group per core, thread = digit dg;
@@ -497,51 +527,47 @@ __device__ __forceinline__ void finish_single_pass(const Dims& d, int t, int dg,
     if (dg == 0 && S == 256) shifted(P.off[t], psh)[256] = N;
     return;
   }
-  // chunk SLOTS (where a chunk's d core_1 partial lives) are contiguous per slice; the DISPATCH
-  // order (index into chunk_rec = blockIdx of the contraction kernels) puts all full chunks
-  // first and the partial ones after: work-groups go round-robin over the 8 XCDs, and a
-  // slice-major list (full, partial, full, partial, ..) would hand every full chunk to the
-  // even XCDs.  Largest-first is also the order a greedy dispatcher balances best.
+  // chunk SLOTS (where a chunk's d core_1 partial lives) are contiguous per slice, full chunks
+  // first; the DISPATCH order (index into chunk_rec = blockIdx of the contraction kernels) is
+  // the slot order dealt column-major over P.cols = 8 columns (chunk_dispatch_index): work-groups
+  // go round-robin over the 8 XCDs, so all chunks of a slice run on ONE XCD, close together in
+  // time, and its L2 fetches the slice's core_1 block from the fabric once instead of once per
+  // chunk.  A column is a run of ~S/8 whole slices, so full and partial chunks spread evenly
+  // over the XCDs (a slice-major list in slot order would hand every full chunk to the even ones).
   const int MC = P.MC;
   const int nf = dg < S ? tot / MC : 0;            // full chunks
-  const int pr = dg < S ? tot - nf * MC : 0;       // lookups in the partial chunk
-  const int np = pr ? 1 : 0;
+  const int np = (dg < S && tot > nf * MC) ? 1 : 0;  // the partial chunk
+  const int nch = nf + np;                         // chunks of this slice: the full ones, then the partial one
   const int nhot = __syncthreads_count(nf + np > kHotRowsPivot);
   if (dg == 0) hdr[8 + 1] = nhot;
-  const int packed = (nf << 12) | np;              // slices <= 256: np sums stay < 4096
-  const int cinc = wave_incl_scan(packed);
+  const int cinc = wave_incl_scan(nch);
   __syncthreads();
   if (lane == kWave - 1 && w < kMbUnits) wt5[w] = cinc;  // (digits live in the first 256 threads)
   __syncthreads();
-  int cb = 0, call = 0;
-  for (int k = 0; k < kMbUnits; ++k) { const int v = wt5[k]; if (k < w) cb += v; call += v; }
-  const int exq = cb + cinc - packed;
-  const int fbase = exq >> 12, pbase = exq & 4095;  // full / partial chunks of earlier slices
-  const int ftot = call >> 12, ptot = call & 4095;
-  const int ctot = ftot + ptot;
-  const int ex = fbase + pbase;                     // first slot of this slice
-  // the records are written by ALL threads, one full chunk each per round (a skewed stream puts hundreds of full
-  // chunks on one slice: its thread writing them one after the other was the tail of the launch): slice dg
-  // publishes {first full chunk, first position, first slot} and every thread finds its chunk's slice by binary
-  // search over the full-chunk prefix
-  __shared__ int cf_base[257], cf_pos[256], cf_slot[256];
+  int cb = 0, ctot = 0;
+  for (int k = 0; k < kMbUnits; ++k) { const int v = wt5[k]; if (k < w) cb += v; ctot += v; }
+  const int ex = cb + cinc - nch;                   // first slot of this slice
+  // the records are written by ALL threads, one chunk each per round (a skewed stream puts hundreds of chunks on
+  // one slice: its thread writing them one after the other was the tail of the launch): slice dg publishes
+  // {first slot, first position, lookups} and every thread finds its slot's slice by binary search over the
+  // slot prefix
+  __shared__ int cf_slot[256], cf_pos[256], cf_tot[256];
   if (dg < S) {
     chunk_off[dg] = ex;
-    cf_base[dg] = fbase;
-    cf_pos[dg] = dbase;
     cf_slot[dg] = ex;
-    if (np) chunk_rec[ftot + pbase] = make_int4(dg, dbase + nf * MC, pr, ex + nf);
+    cf_pos[dg] = dbase;
+    cf_tot[dg] = tot;
   }
-  if (dg == 0) cf_base[S] = ftot;
   __syncthreads();
-  for (int c = threadIdx.x; c < ftot; c += blockDim.x) {
-    int lo = 0, hi = S;  // the last slice with cf_base <= c (slices without full chunks share their successor's base)
+  const ChunkCols cols = chunk_cols(ctot, P.cols);
+  for (int c = threadIdx.x; c < ctot; c += blockDim.x) {
+    int lo = 0, hi = S;  // the last slice with cf_slot <= c (slices without chunks share their successor's first slot)
     while (hi - lo > 1) {
       const int mid = (lo + hi) >> 1;
-      if (cf_base[mid] <= c) lo = mid; else hi = mid;
+      if (cf_slot[mid] <= c) lo = mid; else hi = mid;
     }
-    const int j = c - cf_base[lo];
-    chunk_rec[c] = make_int4(lo, cf_pos[lo] + j * MC, MC, cf_slot[lo] + j);
+    const int j = c - cf_slot[lo];
+    chunk_rec[chunk_dispatch_index(cols, c)] = make_int4(lo, cf_pos[lo] + j * MC, min(MC, cf_tot[lo] - j * MC), c);
   }
   for (int cc = ctot + dg; cc < P.max_chunks; cc += blockDim.x) chunk_rec[cc] = make_int4(0, 0, 0, 0);
   if (dg == 0) {
@@ -967,35 +993,36 @@ __device__ __forceinline__ void finish_wide(const Dims& d, int t, const int (&to
     return;
   }
   const int MC = P.MC;
-  int nf[K], pr[K], packed[K], psum = 0;  // full chunks, lookups of the partial chunk, (full << 12) | partial
+  int nf[K], pr[K], psum = 0;  // full chunks, lookups of the partial chunk; psum = this thread's chunks
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const int dg = tid * K + j;
     nf[j] = dg < S ? tot[j] / MC : 0;
     pr[j] = dg < S ? tot[j] - nf[j] * MC : 0;
-    packed[j] = (nf[j] << 13) | (pr[j] ? 1 : 0);  // <= 4096 slices: the partial counts stay below 8192 (full chunks: < 2^18 on this route)
-    psum += packed[j];
+    psum += nf[j] + (pr[j] ? 1 : 0);
   }
   const int cinc = wave_incl_scan(psum);
   __syncthreads();
   if (lane == kWave - 1) wt[w] = cinc;
   __syncthreads();
-  int cb = 0, call = 0;
-  for (int k = 0; k < kWideWaves; ++k) { const int v = wt[k]; if (k < w) cb += v; call += v; }
-  int exq = cb + cinc - psum;
-  const int ftot = call >> 13, ptot = call & 8191;
-  const int ctot = ftot + ptot;
+  int cb = 0, ctot = 0;
+  for (int k = 0; k < kWideWaves; ++k) { const int v = wt[k]; if (k < w) cb += v; ctot += v; }
+  int ex = cb + cinc - psum;  // first slot of the thread's first slice
+  // the dispatch order of finish_single_pass: the slots dealt column-major over P.cols columns
+  const ChunkCols cols = chunk_cols(ctot, P.cols);
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const int dg = tid * K + j;
-    const int fbase = exq >> 13, pbase = exq & 8191;  // full / partial chunks of earlier slices
-    const int ex = fbase + pbase;                     // first slot of this slice
     if (dg < S) {
       P.chunk_off[dg] = ex;
-      for (int jj = 0; jj < nf[j]; ++jj) P.chunk_rec[fbase + jj] = make_int4(dg, dbase[j] + jj * MC, MC, ex + jj);
-      if (pr[j]) P.chunk_rec[ftot + pbase] = make_int4(dg, dbase[j] + nf[j] * MC, pr[j], ex + nf[j]);
+      if (nf[j] || pr[j]) {
+        ChunkWalk cw = chunk_walk(cols, ex);
+        for (int jj = 0; jj < nf[j]; ++jj)
+          P.chunk_rec[chunk_walk_next(cols, cw)] = make_int4(dg, dbase[j] + jj * MC, MC, ex + jj);
+        if (pr[j]) P.chunk_rec[chunk_walk_next(cols, cw)] = make_int4(dg, dbase[j] + nf[j] * MC, pr[j], ex + nf[j]);
+      }
     }
-    exq += packed[j];
+    ex += nf[j] + (pr[j] ? 1 : 0);
   }
   for (int cc = ctot + tid; cc < P.max_chunks; cc += kWideThreads) P.chunk_rec[cc] = make_int4(0, 0, 0, 0);
   int nh = 0;  // hot pivot slices (reduce_apply: more chunk partials than kHotRowsPivot); the thin cores' blocks write their own word
@@ -1455,9 +1482,9 @@ static int plan_build_mb(const Dims& d, int N, const int* n_dev, const int64_t* 
     return TTX_OK;
   }
   // (tables of different row factors, d.tab: only the wide-digit and the multi-pass plan decode them)
-  // (finish_wide packs a slice's full-chunk count into the upper 18 bits of an int32 prefix sum: the route is for fewer than 2^18
-  //  full chunks -- always, unless the generic kernels' last-resort tile or the test knob leaves MC = 1 with more than 262,144
-  //  lookups; those take the passes below)
+  // (the bound of 2^18 full chunks is historical: finish_wide once packed a slice's full-chunk count into the upper 18 bits of an
+  //  int32 prefix sum.  Nothing needs it any more; it is kept only so that no batch changes its route.  It bites only where the
+  //  generic kernels' last-resort tile or the test knob leaves MC = 1 with more than 262,144 lookups)
   if ((maxp > 1 || d.tab) && (N + kWideSpan - 1) / kWideSpan <= kWideMaxG && N / (P.MC > 0 ? P.MC : 1) < (1 << 18)) {  // one wide digit instead of two passes?
     int smax = 1;
     for (int t = 0; t < d.T; ++t) if (d.S[t] > smax) smax = d.S[t];

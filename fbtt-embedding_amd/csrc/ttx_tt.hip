@@ -2136,6 +2136,7 @@ int ttx_debug_skip(int32_t mask) {
   g_disable_spec = (mask & 256) ? 1 : 0;  // bit 8: force the generic kernels (A/B tests)
   g_disable_pad = (mask & 32768) ? 1 : 0;  // bit 15: shape-specialised kernels for exact shapes only (A/B tests)
   g_no_pack = (mask >> 16) & 1;           // bit 16: no wave-per-slice packing in reduce_apply (results stay valid)
+  g_chunk_cols = (mask >> 17) & 1 ? 1 : kChunkCols;  // bit 17: the pivot's chunk list in slot order, not dealt over 8 columns (plans built from here on; results stay valid)
   g_skip_launch = (mask >> 9) & 63;       // bits 9..11: leave out the pooling launch / reduce_apply / reduce_apply's pivot slices (upper bounds); bit 12: no fused pooling (A/B)
   mask &= 255;
   g_debug_skip = mask;
@@ -2179,7 +2180,7 @@ int ttx_debug_tiles(const ttx_geom* g, int32_t* out) {
 // there, and bench.py refuses to time a library where it is not.  In libttx_hooks.so the knobs are plain globals -- not per
 // stream, not thread-safe: tests and A/B timing only.
 int ttx_debug_state(void) {
-  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
+  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack | (g_chunk_cols != kChunkCols)) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
          (g_chunk_override ? 4 : 0) | (g_stamps ? 8 : 0) | (ttx_cache_debug_state() << 4);
 }
 

@@ -22,7 +22,9 @@ int ttx_set_chunk(int32_t indices_per_chunk);
 int ttx_debug_lds_budget(int32_t bytes);
 /* bit mask: bits 0..7 kernel phases to skip (results INVALID), bit 8 force the generic kernels, bits 9..12 leave out launches,
  * bit 15 shape-specialised kernels for exact shapes only; bit 16 reduce_apply with a work-group per small slice instead of a wave
- * per slice (round 6; results stay valid up to the order of addition).  0 = normal operation. */
+ * per slice (round 6; results stay valid up to the order of addition); bit 17 plans built while it is set list the pivot's chunks
+ * in slot order (one column) instead of dealing the slots column-major over 8 columns, one per XCD (the order is
+ * performance only: results stay bit-identical).  0 = normal operation. */
 int ttx_debug_skip(int32_t mask);
 /* A/B knob (scripts/bench_cache.py): 1 = ttx_cache_forward uses the one-group-per-lookup kernel for every D */
 int ttx_debug_cache_fwd(int32_t lookup_groups);
