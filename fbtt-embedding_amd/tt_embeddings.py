@@ -190,6 +190,12 @@ def _load(path):
     L.ttx_cache_populate_t_workspace_bytes.argtypes = [G, i64, i64, i32]
     L.ttx_cache_populate_t.argtypes = [G, vp, i64, vp, vp, vp, i64, i32, vp, i64, i32, vp, sz, vp]
     L.ttx_cache_forward_n.argtypes = [i32, i64, vp, vp, vp, i32, vp, vp, vp]
+    # ... over tables of different row factors: a host array of num_tables + 1 key bases in the place of the one stride
+    L.ttx_table_keys_v.argtypes = [i64, vp, i32, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.ttx_table_keys_split_v.argtypes = [i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ttx_cache_populate_v_workspace_bytes.restype = C.c_size_t
+    L.ttx_cache_populate_v_workspace_bytes.argtypes = [G, i64, i64, i32]
+    L.ttx_cache_populate_v.argtypes = [G, vp, i64, vp, vp, vp, i64, i32, vp, i32, vp, sz, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
@@ -620,12 +626,37 @@ def cache_populate(num_embeddings: int, tt_p_shapes, tt_q_shapes, tt_ranks, tt_c
                                        ws.data_ptr(), ws.numel(), st))
 
 
-def table_keys(indices: torch.Tensor, offsets: torch.Tensor, num_tables: int, key_stride: int,
+def _key_bases(key_stride, num_tables: int):
+    """`key_stride` of table_keys / table_keys_split: an int is the one stride of tables of one row shape (-> None); a sequence
+    is the num_tables + 1 key bases of tables of different row factors (-> the host int64 array the `_v` calls read)."""
+    if hasattr(key_stride, "__index__"):  # (an int, numpy's integers)
+        return None
+    bases = [int(v) for v in key_stride]
+    if len(bases) != num_tables + 1:
+        raise RuntimeError(f"tt_embeddings: {num_tables} tables need {num_tables + 1} key bases, got {len(bases)}")
+    return (C.c_int64 * len(bases))(*bases)
+
+
+def key_bases_of(tt_p_shapes) -> List[int]:
+    """the key bases of tables of different row factors (include/ttx.h, "row cache over tables of different row factors"):
+    the running sum of the tables' prod(p), num_tables + 1 entries, the last one the size of the key space"""
+    bases = [0]
+    for p in tt_p_shapes:
+        rows = 1
+        for v in p:
+            rows *= int(v)
+        bases.append(bases[-1] + rows)
+    return bases
+
+
+def table_keys(indices: torch.Tensor, offsets: torch.Tensor, num_tables: int, key_stride,
                hashtbl: Optional[torch.Tensor] = None, cache_freq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Not in the reference: the keys of a table-major batch in the row cache over several tables (include/ttx.h, "row cache
     over several tables") -- keys[n] = indices[n] + table(n) * key_stride, the table read off the batch's bag `offsets`
     (num_tables * B + 1 entries, closing entry included).  With `hashtbl` / `cache_freq` the same launch counts the keys, as
-    update_cache_state(keys, hashtbl, cache_freq) would.  -> keys [nnz] int64."""
+    update_cache_state(keys, hashtbl, cache_freq) would.  `key_stride` may be a sequence of num_tables + 1 key bases instead
+    (tables of different row factors, `key_bases_of`): keys[n] = indices[n] + key_stride[table(n)] (ttx_table_keys_v).
+    -> keys [nnz] int64."""
     dev = _dev(indices)
     indices, offsets = _i64(indices, "indices"), _i64(offsets, "offsets")
     nnz, nb = indices.numel(), offsets.numel() - 1
@@ -639,26 +670,30 @@ def table_keys(indices: torch.Tensor, offsets: torch.Tensor, num_tables: int, ke
         _i64(hashtbl, "hashtbl"), _i64(cache_freq, "cache_freq")
         if hashtbl.device != dev or cache_freq.device != dev:
             raise RuntimeError(f"tt_embeddings: hashtbl and cache_freq must be on {dev}")
+    bases = _key_bases(key_stride, num_tables)
     keys = torch.empty_like(indices)
     if nnz == 0:
         return keys
     with _guard(dev):
-        _check(lib().ttx_table_keys(nnz, indices.data_ptr(), num_tables, nb // num_tables, offsets.data_ptr(), int(key_stride),
-                                    keys.data_ptr(), hashtbl.numel() if count else 0, hashtbl.data_ptr() if count else None,
-                                    cache_freq.data_ptr() if count else None, _stream(dev)))
+        call = lib().ttx_table_keys if bases is None else lib().ttx_table_keys_v
+        _check(call(nnz, indices.data_ptr(), num_tables, nb // num_tables, offsets.data_ptr(),
+                    int(key_stride) if bases is None else bases, keys.data_ptr(), hashtbl.numel() if count else 0,
+                    hashtbl.data_ptr() if count else None, cache_freq.data_ptr() if count else None, _stream(dev)))
     return keys
 
 
-def table_keys_split(keys: torch.Tensor, bagrow: Optional[torch.Tensor], num_tables: int, B: int, key_stride: int,
+def table_keys_split(keys: torch.Tensor, bagrow: Optional[torch.Tensor], num_tables: int, B: int, key_stride,
                      n_dev: Optional[torch.Tensor] = None
                      ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Not in the reference: the inverse of table_keys on the first *n_dev entries (one int32 on the device; None: all).  With
     `bagrow` (flat bag rows table * B + b: the prow of preprocess_indices_async over keys) -> (indices, tableidx, rowidx) of
     those entries, what make_plan(n_dev=) takes for the misses; with bagrow None the table is keys // key_stride and rowidx is
-    None.  Entries at and beyond the count are not written (uninitialised)."""
+    None.  Entries at and beyond the count are not written (uninitialised).  `key_stride` may be a sequence of num_tables + 1
+    key bases instead (ttx_table_keys_split_v): with bagrow None the table is then the last one whose base is <= the key."""
     dev = _dev(keys)
     keys = _i64(keys, "keys")
     n = keys.numel()
+    bases = _key_bases(key_stride, num_tables)
     out_i, out_t = torch.empty_like(keys), torch.empty_like(keys)
     out_r = None
     if bagrow is not None:
@@ -669,9 +704,10 @@ def table_keys_split(keys: torch.Tensor, bagrow: Optional[torch.Tensor], num_tab
     if n == 0:
         return out_i, out_t, out_r
     with _guard(dev):
-        _check(lib().ttx_table_keys_split(n, None if n_dev is None else _skip_ptr(n_dev, dev), num_tables, B, int(key_stride),
-                                          keys.data_ptr(), None if bagrow is None else bagrow.data_ptr(), out_i.data_ptr(),
-                                          out_t.data_ptr(), None if out_r is None else out_r.data_ptr(), _stream(dev)))
+        call = lib().ttx_table_keys_split if bases is None else lib().ttx_table_keys_split_v
+        _check(call(n, None if n_dev is None else _skip_ptr(n_dev, dev), num_tables, B, int(key_stride) if bases is None else bases,
+                    keys.data_ptr(), None if bagrow is None else bagrow.data_ptr(), out_i.data_ptr(), out_t.data_ptr(),
+                    None if out_r is None else out_r.data_ptr(), _stream(dev)))
     return out_i, out_t, out_r
 
 
@@ -701,6 +737,36 @@ def cache_populate_tables(num_tables: int, tt_p_shapes, tt_q_shapes, tt_ranks, t
         _check(lb.ttx_cache_populate_t(C.byref(g), _ptr_array(cores), H, hashtbl.data_ptr(), cache_freq.data_ptr(),
                                        cache_state.data_ptr(), cs, D, cw.data_ptr(), int(key_stride),
                                        1 if reference_exact else 0, ws.data_ptr(), ws.numel(), st))
+
+
+def cache_populate_var_tables(tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores, hashtbl, cache_freq, cache_state, cache_weight,
+                              reference_exact: bool = False) -> None:
+    """Not in the reference: cache_populate for the row cache over tables of DIFFERENT row factors (`tt_p_shapes`: one list per
+    table; cores [1, sum_k p_k_t, slice]), whose hash table holds keys key_bases_of(tt_p_shapes)[table] + index
+    (ttx_cache_populate_v): the cache_size most frequent keys get the cache rows, each decompressed from its own table's cores."""
+    if len(tt_p_shapes) == 0 or not isinstance(tt_p_shapes[0], (list, tuple)):
+        raise RuntimeError("tt_embeddings: cache_populate_var_tables takes one list of row factors per table")
+    g = _geom_mixed(tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(cache_weight)
+    cores = _cores(list(tt_cores), g)
+    H = hashtbl.numel()
+    if H <= 0 or H != cache_freq.numel() or H < cache_weight.size(0):
+        raise RuntimeError("tt_embeddings: need 0 < hashtbl.numel() == cache_freq.numel() >= cache_size")
+    _i64(hashtbl, "hashtbl"), _i64(cache_freq, "cache_freq")
+    if cache_state.dtype != torch.int32 or cache_state.numel() != H:
+        raise RuntimeError("tt_embeddings: cache_state must be int32[hashtbl_size]")
+    cw = cache_weight.detach()
+    if cw.dtype != torch.float32 or not cw.is_contiguous():
+        raise RuntimeError("tt_embeddings: cache_weight must be contiguous float32")
+    cs, D = cw.size(0), cw.size(1)
+    lb = lib()
+    st = _stream(dev)
+    with _guard(dev):
+        nb = lb.ttx_cache_populate_v_workspace_bytes(C.byref(g), H, cs, D)
+        ws = _workspace(dev, st, nb)
+        _check(lb.ttx_cache_populate_v(C.byref(g), _ptr_array(cores), H, hashtbl.data_ptr(), cache_freq.data_ptr(),
+                                       cache_state.data_ptr(), cs, D, cw.data_ptr(), 1 if reference_exact else 0,
+                                       ws.data_ptr(), ws.numel(), st))
 
 
 def preprocess_indices_sync(colidx: torch.Tensor, offsets: torch.Tensor, num_tables: int, warmup: bool,

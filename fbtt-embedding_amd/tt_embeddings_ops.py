@@ -32,7 +32,8 @@ Deliberate differences (each is a superset or a fix):
     TTRowsLookupFunction below), on the ctypes route;
   * one row cache over the tables of a table-batched bag: `TableBatchedTTEmbeddingBag(num_tables > 1, use_cache=True)` (the
     reference asserts one table, :456) keys one hash table / cache_weight by table * prod(tt_p_shapes) + index
-    (TTTablesCachedLookupFunction below, DESIGN.md 4.13), on the ctypes route;
+    (TTTablesCachedLookupFunction below), on the ctypes route -- and, for tables of different row factors
+    (ttx_mixed.VarTableTTEmbeddingBag(use_cache=True), DESIGN.md 4.14), by key_base[table] + index through the same node;
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -583,12 +584,15 @@ class TTTablesCachedLookupFunction(torch.autograd.Function):
     table_keys_split of the misses back to (index, table, bag row), the plan of the misses (make_plan(n_dev=split point)), their
     contraction and pooling (tt_forward) and cache_forward(skip_dev=split point) for the hits.  Backward: the fused SGD /
     Adagrad or dense backward on the plan, and the cache rows' update with rowidx = the flat bag rows and skip_dev = the split
-    point: SGD, row-wise Adagrad, or the dense gradient of cache_weight (returned in its slot).  Nothing is read back."""
+    point: SGD, row-wise Adagrad, or the dense gradient of cache_weight (returned in its slot).  Nothing is read back.
+    Tables of DIFFERENT row factors (ttx_mixed.VarTableTTEmbeddingBag) run the same node: `tt_p_shapes` is then
+    one list per table (cores [1, sum_k p_k_t, slice]) and `key_stride` the list of the num_tables + 1 key bases,
+    key = key_stride[table] + index -- the engine's key calls take either."""
 
     N_ARGS, CACHE_WEIGHT_ARG = 21, 19
 
     @staticmethod
-    def forward(ctx, B: int, D: int, num_tables: int, key_stride: int, tt_p_shapes: List[int], tt_q_shapes: List[int],
+    def forward(ctx, B: int, D: int, num_tables: int, key_stride, tt_p_shapes: List[int], tt_q_shapes: List[int],
                 tt_ranks: List[int], L: torch.Tensor, indices: torch.Tensor, offsets: torch.Tensor, hashtbl: torch.Tensor,
                 cache_state: torch.Tensor, cache_freq: Optional[torch.Tensor], det: Optional[bool], optimizer: OptimType,
                 learning_rate: float, eps: float, sparse: bool, cache_optimizer_state: Optional[torch.Tensor],
@@ -967,6 +971,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         index decode covers (>= num_embeddings)"""
         return int(np.prod(np.asarray(self.tt_p_shapes, dtype=np.int64)))
 
+    def _key_space(self):
+        """what the key calls take in the place of `key_stride`: the one stride -- or, where a subclass batches tables of different
+        row factors, the list of its num_tables + 1 key bases (ttx_mixed.VarTableTTEmbeddingBag)"""
+        return self._key_stride()
+
     def _tables_cache(self) -> bool:
         """one row cache over several tables"""
         return bool(self.use_cache) and self.num_tables > 1
@@ -976,13 +985,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         (table_keys with the count folded in), torch ops on CPU tensors (the tests' oracle engine)."""
         if indices.numel() == 0:
             return
+        space = self._key_space()
         if indices.is_cuda and getattr(_engine, "table_keys", None) is not None:
-            _engine.table_keys(indices, offsets, self.num_tables, self._key_stride(), self.hashtbl, self.cache_freq)
+            _engine.table_keys(indices, offsets, self.num_tables, space, self.hashtbl, self.cache_freq)
             return
         B = (offsets.numel() - 1) // self.num_tables
         bounds = offsets[::B][1:self.num_tables].contiguous()  # the first position of tables 1 .. num_tables - 1
         table = torch.bucketize(torch.arange(indices.numel(), dtype=torch.int64, device=indices.device), bounds, right=True)
-        _engine.update_cache_state((indices + table * self._key_stride()).contiguous(), self.hashtbl, self.cache_freq)
+        if isinstance(space, (list, tuple)):  # (key bases: one per table)
+            first = torch.tensor(list(space[:-1]), dtype=torch.int64, device=indices.device)[table]
+        else:
+            first = table * space
+        _engine.update_cache_state((indices + first).contiguous(), self.hashtbl, self.cache_freq)
 
     def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1) -> None:
         """tt_embeddings_ops.py:800-814.  `write_back` (NOT in the reference; default 0 = its behaviour): cached rows are trained
@@ -1483,8 +1497,9 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                              f"{self.num_tables} tables")
         fast = _native_node()
         count_local = d["use_cache"]  # the route's own frequency update counts the indices as they are (one table)
-        if count_local and d["num_tables"] > 1:
+        if count_local and (d["num_tables"] > 1 or self._tables_cache()):
             # ONE row cache over all tables: the frequency table holds keys table * key_stride + index
+            # (tables of different row factors, DESIGN.md 4.14: key_base[table] + index -- `_key_space`)
             count_local = False
             if not self.warmup and indices.numel() > 0:
                 if not indices.is_cuda or getattr(_engine, "table_keys", None) is None:
@@ -1493,7 +1508,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                     raise NotImplementedError("per_sample_weights with a live row cache over several tables")
                 use_state, _ = _optim_code(self.sparse, self.optimizer)
                 return TTTablesCachedLookupFunction.apply(
-                    (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.num_tables, self._key_stride(),
+                    (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.num_tables, self._key_space(),
                     self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, self.L, indices.contiguous(), offsets.contiguous(),
                     self.hashtbl, self.cache_state, self.cache_freq, d.get("deterministic_cache_update"), self.optimizer,
                     self.learning_rate, self.eps, self.sparse, self.cache_optimizer_state if use_state else None,

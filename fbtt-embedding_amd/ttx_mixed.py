@@ -56,7 +56,8 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
     forward, one backward launch set for all of them (include/ttx.h `ttx_geom::p_tables`).  Core t is one
     Parameter [1, sum_k p_k_t, r_t q_t r_{t+1}] holding the tables' slices one table after the other
     (`table_rows(t)[k]` = table k's rows of it); forward takes the table-major batched form, like the parent,
-    and returns [num_tables, B, D].  No cache (the parent allows one for a single table only)."""
+    and returns [num_tables, B, D].  `use_cache=True`: ONE LFU row cache over all the tables, keyed by key_base[table] + index
+     -- the hottest rows across tables of any cardinality behind one hash table and one launch set."""
 
     def __init__(self, num_embeddings: Sequence[int], embedding_dim: int, tt_ranks: List[int],
                  tt_p_shapes: Optional[Sequence[Optional[List[int]]]] = None, tt_q_shapes: Optional[List[int]] = None,
@@ -64,8 +65,16 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True,
                  table_ranks: Optional[Sequence[List[int]]] = None, table_q: Optional[Sequence[List[int]]] = None,
-                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
-        """`mode`, `padding_idx` (trailing keywords, as on the parent): nn.EmbeddingBag's pooling modes and padded batches, on the
+                 mode: str = "sum", padding_idx: Optional[int] = None, use_cache: bool = False, cache_size: int = 0,
+                 hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None,
+                 reference_exact_populate: bool = False) -> None:
+        """`use_cache`, `cache_size`, `hashtbl_size`, `deterministic_cache_update`, `reference_exact_populate` (trailing keywords, as
+        on the parent): ONE LFU row cache over all the tables, keyed by key_base[table] + index with key_base the
+        running sum of the tables' prod(p) (`_key_space`).  Same buffers, parameters and state_dict() keys as the one-table cached
+        module; defaults cache_size = int(0.1 * sum_k E_k), hashtbl_size = sum_k E_k.  Warm-up counts the batch's keys in one
+        extra launch and runs the uncached routes; after cache_populate() the live route of the parent's table cache runs on the
+        per-table row factors (TTTablesCachedLookupFunction).  Three cores only, no `table_q`, no mode="max"; GPU tensors once live.
+        `mode`, `padding_idx` (trailing keywords, as on the parent): nn.EmbeddingBag's pooling modes and padded batches, on the
         parent's routes -- forward also takes the 2-D form `indices[num_tables * B, L]` with `offsets=None`.  `padding_idx` is ONE
         value for all tables, so it has to be a row of every one of them: torch's rule against the smallest cardinality.
         `table_q` (one factoring per table, entry by entry <= `tt_q_shapes`, every one a factoring of `embedding_dim`; round 4):
@@ -112,6 +121,28 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
             assert tt_q_shapes is not None and len(self.table_q) == len(Es), "table_q: with the common tt_q_shapes, one per table"
             assert all(len(q) == nd and int(np.prod(q)) == self.out_dim and all(a <= b for a, b in zip(q, self.tt_q_shapes))
                        for q in self.table_q), "table_q: per table a factoring of embedding_dim, entry by entry <= tt_q_shapes"
+        self.deterministic_cache_update = deterministic_cache_update
+        self.reference_exact_populate = bool(reference_exact_populate)
+        if use_cache:
+            # the limits of the row cache over tables of different row factors, by name and before anything is built
+            if mode == "max":
+                raise NotImplementedError("mode='max' does not support use_cache=True (the cache rows are pooled by sum)")
+            if nd != 3:
+                # (the populate decompresses rows with ttx_tt_rows on a plan with per-table row factors, which has only ever run
+                #  with three cores: ttx_cache_populate_v returns TTX_EUNSUPPORTED for any other count)
+                raise NotImplementedError(f"use_cache=True on tables of different row factors needs three TT cores, got {nd}")
+            if self.table_q is not None:
+                raise NotImplementedError("use_cache=True does not support table_q: the cache rows would have the padded row "
+                                          "length, over which row-wise Adagrad would average")
+            cache_size = int(cache_size) if cache_size > 0 else int(0.1 * sum(Es))
+            hashtbl_size = int(hashtbl_size) if hashtbl_size > 0 else sum(Es)
+            if hashtbl_size >= 2 ** 31:
+                raise ValueError(f"hashtbl_size must stay below 2^31, got {hashtbl_size} (the default is the sum of the tables' "
+                                 f"num_embeddings: pass a smaller hashtbl_size)")
+            space = sum(int(np.prod(np.asarray(p, dtype=object))) for p in ps)
+            if space >= 2 ** 62:
+                raise ValueError(f"the cache's key space sum_k prod(tt_p_shapes[k]) = {space} does not fit 2^62")
+            assert hashtbl_size >= cache_size
         self.num_tables, self.tt_ndim = len(Es), nd
         # (the parent's forward sizes its output rows by embedding_dim: the PADDED row length when the factorings differ)
         self.table_num_embeddings, self.embedding_dim = Es, int(np.prod(self.tt_q_shapes))
@@ -156,13 +187,56 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
                     at += np.arange(q[t], dtype=np.int64).reshape(shape) * int(np.prod(self.tt_q_shapes[t + 1:]))
                 cols.append(at.reshape(-1))
             self.register_buffer("_cols", torch.from_numpy(np.stack(cols)).to(device), persistent=False)
-        self.use_cache = False
-        self.register_buffer("hashtbl", torch.empty(0, device=device, dtype=torch.int64))
-        self.register_buffer("cache_freq", torch.empty(0, device=device, dtype=torch.int64))
-        self.register_buffer("cache_state", torch.empty(0, device=device, dtype=torch.int32))
-        self.cache_optimizer_state = None
-        self.cache_weight = None
+        self.use_cache = bool(use_cache)
+        if use_cache:  # (one set for all tables; names, order and shapes as the one-table cached module registers them)
+            self.register_buffer("hashtbl", torch.full((hashtbl_size,), -1, device=device, dtype=torch.int64))
+            self.register_buffer("cache_freq", torch.zeros(hashtbl_size, device=device, dtype=torch.int64))
+            self.register_buffer("cache_state", torch.full((hashtbl_size,), -1, device=device, dtype=torch.int32))
+            self.cache_weight = nn.Parameter(torch.zeros((cache_size, self.embedding_dim), device=device, dtype=torch.float32))
+            if sparse and stateful:
+                shape = (cache_size, self.embedding_dim) if optimizer == OptimType.EXACT_ADAGRAD else (cache_size,)
+                self.register_buffer("cache_optimizer_state", torch.zeros(shape, device=device, dtype=torch.float32))
+            else:
+                self.cache_optimizer_state = None
+        else:
+            self.register_buffer("hashtbl", torch.empty(0, device=device, dtype=torch.int64))
+            self.register_buffer("cache_freq", torch.empty(0, device=device, dtype=torch.int64))
+            self.register_buffer("cache_state", torch.empty(0, device=device, dtype=torch.int32))
+            self.cache_optimizer_state = None
+            self.cache_weight = None
         self.warmup = True
+
+    def _key_space(self) -> List[int]:
+        """the row cache keys a lookup (table k, index i) by key_base[k] + i: the running sum of the tables' prod(p), num_tables + 1
+        entries (include/ttx.h "row cache over tables of different row factors")"""
+        bases = self.__dict__.get("_key_bases")
+        if bases is None:
+            bases = [0]
+            for p in self.tt_p_shapes:
+                bases.append(bases[-1] + int(np.prod(np.asarray(p, dtype=object))))
+            self._key_bases = bases
+        return bases
+
+    def _tables_cache(self) -> bool:
+        """one row cache over the tables, however many (one table included: the parent's one-table routes take one list of row
+        factors)"""
+        return bool(self.use_cache)
+
+    def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1) -> None:
+        """the cache_size most frequent keys get the cache rows, each decompressed from its own table (ttx_cache_populate_v); the
+        cache is live from here on.  GPU only; no `write_back`."""
+        if not self.use_cache:
+            return
+        if write_back > 0.0:
+            raise NotImplementedError("cache_populate(write_back > 0) is not supported by the row cache over several tables")
+        populate = getattr(_ops._engine, "cache_populate_var_tables", None)
+        if populate is None or not self.cache_weight.is_cuda:
+            raise NotImplementedError("the row cache over tables of different row factors is populated on the GPU only")
+        extra = {"reference_exact": True} if self.reference_exact_populate else {}
+        populate(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), self.hashtbl, self.cache_freq,
+                 self.cache_state, self.cache_weight, **extra)
+        self.warmup = False
+        self._drop_prefetched()
 
     def _table_dims(self, k: int, t: int):
         rk = self.tt_ranks if self.table_ranks is None else self.table_ranks[k]
@@ -263,6 +337,11 @@ class MixedTTEmbeddingBag(nn.Module):
     `mode`, `padding_idx` (trailing keywords): nn.EmbeddingBag's pooling modes and padded batches as on the uniform modules
     (DESIGN.md 4.9 - 4.11).  `padding_idx` is None, one int, or one entry (int or None) per table, each normalised against its own
     table's cardinality.
+    `use_cache=True` (with fused=True): every fused group gets ONE LFU row cache over its tables
+    (`VarTableTTEmbeddingBag(use_cache=True)`).  A positive `cache_size` / `hashtbl_size` is the total over the groups, split in
+    proportion to their summed cardinalities (rounded down, at least 1 each); 0 gives every group its default.  `cache_populate()`,
+    `reset_cache()` and `update_cache(indices, offsets)` (per-table lists) fan out to the groups.  A group that would need
+    `table_q` is refused: `pad_q=False` avoids it.
     forward(indices, offsets[, per_sample_weights]) takes one tensor per table (nn.EmbeddingBag call form,
     `include_last_offset` as given to the constructor; or, per table, 2-D `indices[k]` [B, L_k] with `offsets[k] = None`) and
     returns one [B, D] tensor per table.  On GPU tensors a group's table-major batch is ONE launch (`ttx_bags_merge`)."""
@@ -273,8 +352,13 @@ class MixedTTEmbeddingBag(nn.Module):
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = False,
                  streams: bool = False, fused: bool = False, pad_ranks: Optional[bool] = None,
-                 pad_q: Optional[bool] = None, mode: str = "sum", padding_idx=None) -> None:
+                 pad_q: Optional[bool] = None, mode: str = "sum", padding_idx=None, use_cache: bool = False,
+                 cache_size: int = 0, hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None) -> None:
         super().__init__()
+        if use_cache and not fused:
+            raise NotImplementedError("use_cache=True needs fused=True: the row cache is one per fused group "
+                                      "(VarTableTTEmbeddingBag(use_cache=True))")
+        self.use_cache = bool(use_cache)
         self.num_embeddings = [int(e) for e in num_embeddings]
         n = len(self.num_embeddings)
         if mode not in POOLING_MODES:
@@ -360,17 +444,31 @@ class MixedTTEmbeddingBag(nn.Module):
             groups.setdefault(key, []).append(k)
         self.group_tables = list(groups.values())
         self.groups = nn.ModuleList()
+        # use_cache: every fused group gets a cache of its own.  A positive cache_size / hashtbl_size is the TOTAL over the groups,
+        # split in proportion to the groups' summed cardinalities (rounded down, at least 1 each); 0: every group's own default
+        total_rows = sum(self.num_embeddings)
         for tables in self.group_tables:
             k0 = tables[0]
+            cache_kw = {}
+            if use_cache:
+                share = sum(self.num_embeddings[k] for k in tables)
+                cache_kw = dict(use_cache=True, deterministic_cache_update=deterministic_cache_update,
+                                cache_size=max(1, int(cache_size) * share // total_rows) if cache_size > 0 else 0,
+                                hashtbl_size=max(1, int(hashtbl_size) * share // total_rows) if hashtbl_size > 0 else 0)
             if fused:  # ONE batched lookup for the group's tables, whatever their row factors (VarTableTTEmbeddingBag)
                 rmax = [max(ranks[k][i] for k in tables) for i in range(len(ranks[k0]))]
                 mixed_ranks = any(ranks[k] != rmax for k in tables)
                 qmax = [max(qs[k][i] for k in tables) for i in range(len(qs[k0]))]
                 mixed_q = any(qs[k] != qmax for k in tables)
+                if use_cache and mixed_q:
+                    raise NotImplementedError(f"use_cache=True: tables {tables} share one launch set over a padded factoring "
+                                              f"(table_q), which the row cache does not serve -- pad_q=False keeps one group (and "
+                                              f"one cache) per factoring")
                 self.groups.append(VarTableTTEmbeddingBag(
                     [self.num_embeddings[k] for k in tables], self.embedding_dim, rmax, [list(shapes[k]) for k in tables],
                     qmax, optimizer, learning_rate, eps, sparse, weight_dist, enforce_embedding_dim, device, True,
-                    [ranks[k] for k in tables] if mixed_ranks else None, [qs[k] for k in tables] if mixed_q else None, mode))
+                    [ranks[k] for k in tables] if mixed_ranks else None, [qs[k] for k in tables] if mixed_q else None, mode,
+                    **cache_kw))
             else:
                 self.groups.append(TableBatchedTTEmbeddingBag(
                     len(tables), max(self.num_embeddings[k] for k in tables), self.embedding_dim, list(ranks[k0]),
@@ -384,6 +482,31 @@ class MixedTTEmbeddingBag(nn.Module):
                 mod.padding_idx = PAD_SENTINEL
         self._streams = [torch.cuda.Stream(device=self.groups[0].tt_cores[0].device) for _ in self.groups] \
             if streams and len(self.groups) > 1 else None
+
+    # ------------------------------------------------------------------ the groups' row caches (use_cache=True)
+    def cache_populate(self) -> None:
+        """every group's cache_populate(): the groups' caches are live from here on"""
+        for mod in self.groups:
+            mod.cache_populate()
+
+    def reset_cache(self) -> None:
+        for mod in self.groups:
+            mod.reset_cache()
+
+    def update_cache(self, indices: Sequence[torch.Tensor], offsets: Sequence[Optional[torch.Tensor]]) -> None:
+        """count a batch -- one (indices, offsets) pair per table, the form forward() takes -- in the groups' frequency tables;
+        padding slots are not counted"""
+        if not self.__dict__.get("use_cache", False):
+            return
+        n = len(self.num_embeddings)
+        assert len(indices) == n and len(offsets) == n, f"one (indices, offsets) pair per table: {n} tables"
+        for mod, tables in zip(self.groups, self.group_tables):
+            idx, off, _ = self._merge(tables, indices, offsets, None)
+            if mod.padding_idx is not None:  # (the merged batch holds PAD_SENTINEL at the padding: torch ops drop it, as forward's
+                keep = idx != mod.padding_idx  # CPU route does; the live count shapes the result -- a host synchronisation)
+                before = torch.cat([torch.zeros(1, dtype=torch.int64, device=idx.device), torch.cumsum(keep, 0)])
+                idx, off = idx[keep], before[off.long().clamp(0, idx.numel())]
+            mod.update_cache(idx, off)
 
     def _merge(self, tables: List[int], indices, offsets, per_sample_weights):
         """the batch of one group, table-major: (indices, offsets with the closing entry, weights or None), every table's padding

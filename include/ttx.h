@@ -656,6 +656,53 @@ int ttx_cache_populate_t(const ttx_geom* g, const float* const* tt_cores, int64_
                          int64_t* cache_freq, int32_t* cache_state, int64_t cache_size, int32_t D, float* cache_weight,
                          int64_t key_stride, int32_t flags, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
 
+/* ------------------------------ row cache over tables of different row factors (not in the reference) -----
+ * The same ONE cache for the tables of a p_tables geometry (tables of different row factors, common q and ranks;
+ * num_tables <= TTX_MAX_TABLES_MIXED).  A single stride no longer separates the tables: table k covers
+ * stride_k = prod_t p_tables[k][t] rows, and a lookup (table k, index i) is the key
+ *
+ *   key = key_base[k] + i,   key_base[k] = sum_{j < k} stride_j,   key_base[num_tables] = the total
+ *
+ * The ranges are disjoint because i < num_embeddings_k <= stride_k.  key_base is a HOST array of num_tables + 1 int64, read
+ * during the call only (as p_tables is): it travels in the kernel arguments -- no call below allocates device memory or copies
+ * from pageable host memory, the first two read nothing back and are capturable in a hipGraph.  Everything said above about
+ * keys in place of indices and bags addressed by their flat row holds unchanged.
+ *
+ *   ttx_table_keys_v        keys[n] = indices[n] + key_base[t(n)], t(n) found exactly as ttx_table_keys finds it: the last
+ *                           of the num_tables + 1 table boundaries offsets[t B] that is <= n (empty tables and empty bags are
+ *                           legal, t(n) always lies in [0, num_tables - 1]).  64-bit arithmetic throughout.  With
+ *                           upd_hashtbl / upd_cache_freq (both or neither; H slots) the launch also counts the keys, exactly
+ *                           as ttx_update_cache_state would.  One launch, one writer per element.
+ *   ttx_table_keys_split_v  the inverse on the first *n_dev entries (a device int32, clamped to [0, n]; NULL: all n).
+ *                           bagrow != NULL: t = bagrow[s] / B clamped to [0, num_tables - 1] before it indexes anything,
+ *                           out_rowidx[s] = bagrow[s] - t B, out_indices[s] = keys[s] - key_base[t], out_tableidx[s] = t.
+ *                           bagrow == NULL (populate): t = the last k in [0, num_tables - 1] with key_base[k] <= keys[s] (a
+ *                           binary search of at most 6 steps; tables of stride 1 are found like any other) and out_rowidx is
+ *                           not written (may be NULL).  Entries at and beyond the count are NOT written.
+ *   ttx_cache_populate_v    ttx_cache_populate_t for a geometry that carries p_tables; key_base is derived from it on the
+ *                           host.  The same sort and mark on the keys, the cache_size selected keys split (bagrow == NULL)
+ *                           and decompressed by ttx_tt_rows on the p_tables geometry, each from its own table; an empty slot
+ *                           among them is row 0 of table 0.  Honours TTX_POPULATE_REFERENCE_EXACT.  T == 3 only (the rows
+ *                           route on per-table row factors has only ever run with three cores): any other T returns
+ *                           TTX_EUNSUPPORTED.  One 8-byte read-back sizes the sort, as in ttx_cache_populate; a geometry seen
+ *                           for the first time places its per-table factors on the device (as in every p_tables call).
+ *   nnz == 0 / n == 0       returns 0 and launches nothing.
+ *   errors                  a negative size, nnz >= 2^31, B <= 0, num_tables outside [1, TTX_MAX_TABLES_MIXED],
+ *                           num_tables * B >= 2^31, key_base NULL, not starting at 0, not strictly increasing or ending at or
+ *                           above 2^62, counting with one of the two tables missing or H outside (0, 2^31), an int64 pointer
+ *                           not 8-byte (n_dev: 4-byte) aligned, a NULL pointer that would be read or written: -1 with
+ *                           ttx_last_error() set, before anything touches a device. */
+int ttx_table_keys_v(int64_t nnz, const int64_t* indices, int32_t num_tables, int64_t B, const int64_t* offsets,
+                     const int64_t* key_base, int64_t* keys, int64_t H, int64_t* upd_hashtbl, int64_t* upd_cache_freq,
+                     ttx_stream_t stream);
+int ttx_table_keys_split_v(int64_t n, const int32_t* n_dev, int32_t num_tables, int64_t B, const int64_t* key_base,
+                           const int64_t* keys, const int64_t* bagrow, int64_t* out_indices, int64_t* out_tableidx,
+                           int64_t* out_rowidx, ttx_stream_t stream);
+size_t ttx_cache_populate_v_workspace_bytes(const ttx_geom* g, int64_t hashtbl_size, int64_t cache_size, int32_t D);
+int ttx_cache_populate_v(const ttx_geom* g, const float* const* tt_cores, int64_t hashtbl_size, int64_t* hashtbl,
+                         int64_t* cache_freq, int32_t* cache_state, int64_t cache_size, int32_t D, float* cache_weight,
+                         int32_t flags, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
+
 /* replaces cache_forward_cuda (tt_embeddings.cpp:97-103,
  * tt_embeddings_cuda.cu:1498-1572): output[rowidx[n], :] += cache_weight[
  * cache_locations[n], :], summed per run of equal rowidx. */
