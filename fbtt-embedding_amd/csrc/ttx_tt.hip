@@ -1170,7 +1170,8 @@ static bool spec_shape(const Dims& d) { return spec_match(d) != SPEC_NONE; }
 template <class S>
 constexpr int mc_of(int ks) { return S::MC * (S::SUB ? ks : 1); }
 static int spec_mc(const Dims& d, long long nnz) {
-  const int ks = nnz >= TTX_SUBCHUNK_NNZ ? TTX_SUBCHUNKS : 1;
+  // (test library: ttx_set_chunk(64) asks for the sub-chunked variant at any batch size -- the walk is otherwise out of a test's reach)
+  const int ks = (nnz >= TTX_SUBCHUNK_NNZ || g_chunk_override == 64) ? TTX_SUBCHUNKS : 1;
   switch (spec_match(d)) {
     case SPEC_32_4_32_4: return mc_of<S_32_4_32_4>(ks);
     case SPEC_16_4_16_4: return mc_of<S_16_4_16_4>(ks);
@@ -2053,12 +2054,12 @@ static int run_rows_spec(TTX_SPEC_FWD_ARGS) {
 }
 
 static int run_bwd_spec(TTX_SPEC_BWD_ARGS) {
-  int rc = spec_bwd_32(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
-  if (rc == kSpecNotMine) rc = spec_bwd_64(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
-  if (rc == kSpecNotMine) rc = spec_bwd_16(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
-  if (rc == kSpecNotMine) rc = spec_bwd_128a(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
-  if (rc == kSpecNotMine) rc = spec_bwd_128b(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
-  if (rc == kSpecNotMine) rc = spec_bwd_128c(id, d, P, C, B, rowidx, d_output, PC, pad, R, st);
+  int rc = spec_bwd_32(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
+  if (rc == kSpecNotMine) rc = spec_bwd_64(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
+  if (rc == kSpecNotMine) rc = spec_bwd_16(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
+  if (rc == kSpecNotMine) rc = spec_bwd_128a(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
+  if (rc == kSpecNotMine) rc = spec_bwd_128b(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
+  if (rc == kSpecNotMine) rc = spec_bwd_128c(id, d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st);
   if (rc == kSpecNotMine) TTX_FAIL(TTX_EUNSUPPORTED, "no specialised backward kernel");
   return rc;
 }
@@ -2137,6 +2138,8 @@ int ttx_debug_skip(int32_t mask) {
   g_disable_pad = (mask & 32768) ? 1 : 0;  // bit 15: shape-specialised kernels for exact shapes only (A/B tests)
   g_no_pack = (mask >> 16) & 1;           // bit 16: no wave-per-slice packing in reduce_apply (results stay valid)
   g_chunk_cols = (mask >> 17) & 1 ? 1 : kChunkCols;  // bit 17: the pivot's chunk list in slot order, not dealt over 8 columns (plans built from here on; results stay valid)
+  g_old_stores = (mask >> 18) & 1;        // bit 18: the shape-specialised backward stores its partial gradients as before -- C/D layout, 4-byte non-temporal (results stay valid)
+  g_partial_flavour = (mask >> 19) & 3;   // bits 19..20: flavour of the 16-byte partial stores forced for every launch: 1 non-temporal, 2 write-through, 3 plain (results stay valid)
   g_skip_launch = (mask >> 9) & 63;       // bits 9..11: leave out the pooling launch / reduce_apply / reduce_apply's pivot slices (upper bounds); bit 12: no fused pooling (A/B)
   mask &= 255;
   g_debug_skip = mask;
@@ -2180,7 +2183,7 @@ int ttx_debug_tiles(const ttx_geom* g, int32_t* out) {
 // there, and bench.py refuses to time a library where it is not.  In libttx_hooks.so the knobs are plain globals -- not per
 // stream, not thread-safe: tests and A/B timing only.
 int ttx_debug_state(void) {
-  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack | (g_chunk_cols != kChunkCols)) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
+  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack | g_old_stores | g_partial_flavour | (g_chunk_cols != kChunkCols)) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
          (g_chunk_override ? 4 : 0) | (g_stamps ? 8 : 0) | (ttx_cache_debug_state() << 4);
 }
 
@@ -2560,7 +2563,7 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
     PC3.pc[3] = nullptr;
     RealDims R = real_dims(d3);
     R.c2n = 1;
-    rc = run_bwd_spec(id, d3, P, C3, B, rowidx, d_output, PC3, pad, R, st);
+    rc = run_bwd_spec(id, d3, P, C3, B, rowidx, d_output, PC3, pad, R, nnz, st);
     if (rc) return rc;
     const int SEG = t4_seg(nnz);
     const size_t lds = (size_t)((n2 + 3) / 4 * 4 + kT4Batch * (pm + n3)) * sizeof(float);
@@ -2623,7 +2626,7 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
     TTX_HIP(hipGetLastError());
   } else if (const SpecId id = spec_match(d, &pad)) {
     ProfScope ps(TTX_PROF_BWD, st);
-    rc = run_bwd_spec(id, d, P, C, B, rowidx, d_output, PC, pad, real_dims(d), st);
+    rc = run_bwd_spec(id, d, P, C, B, rowidx, d_output, PC, pad, real_dims(d), nnz, st);
     if (rc) return rc;
   } else {
     Lds L;

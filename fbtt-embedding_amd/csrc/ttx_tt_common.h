@@ -83,7 +83,11 @@ __device__ __forceinline__ void zero_output(float* __restrict__ out, long long n
 extern int g_debug_skip;
 extern int g_disable_spec;
 extern long long* g_stamps;
+extern int g_old_stores;       // ttx_debug_skip bit 18: partial gradients as 4-byte non-temporal stores (Shape3::W16 off), A/B
+extern int g_partial_flavour;  // ttx_debug_skip bits 19..20: 0 = by the launch's partial bytes, else 1 + the flavour forced (PStore)
 #else
+constexpr int g_old_stores = 0;
+constexpr int g_partial_flavour = 0;
 constexpr int g_debug_skip = 0;
 constexpr int g_disable_spec = 0;
 constexpr long long* g_stamps = nullptr;

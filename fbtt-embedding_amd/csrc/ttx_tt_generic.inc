@@ -47,6 +47,8 @@ static TTX_KNOB(int, g_chunk_override, 0);
 int g_debug_skip = 0;     // (declared in ttx_tt_common.h: the specialised kernels' translation units read them)
 int g_disable_spec = 0;
 long long* g_stamps = nullptr;
+int g_old_stores = 0;
+int g_partial_flavour = 0;
 #endif
 static TTX_KNOB(int, g_lds_budget, 160 * 1024);  // (tests shrink it to drive small shapes through the block walk)
 static bool spec_shape(const Dims& d);  // ttx_tt_spec.inc covers this geometry

@@ -71,6 +71,12 @@ struct Shape3 {
   // kernel, and a plain store parks 17 MB of dirty lines in L2 that the end of the kernel has to write back
   // (measured: step -3.8 % at r = 32, -2.8 % at 327k lookups, +1.4 % at r = 64 -> off there)
   static constexpr bool NT = R1_ <= 32;
+  // ... and (exact shapes) as whole float4s: d core_0 and the cooperative d core_1 are computed TRANSPOSED (MFMA operands swapped:
+  // the same products summed in the same order), so that an accumulator's four registers are four consecutive floats of one partial
+  // row.  A 16-byte store can go write-through (sc1) at the price of a plain one -- a 4-byte one cannot -- which is what lets the
+  // launch choose the flavour by its partial bytes (PStore, partial_store_flavour below).  OldStores<S> switches it off; the
+  // padded variants and the sub-chunk walk (MULTI) do not have it (spec_bwd_kernel).
+  static constexpr bool W16 = NT;
   // large batches may put several sub-chunks of MC lookups into one chunk of the plan (kernel variant MULTI)
   static constexpr bool SUB_ = R1_ <= 32 && Q2_ <= 8;  // (q2 = 16: the walk's operands in flight do not fit the registers)
   // d core_1 of a pass: with as many column tiles as waves (or a multiple), wave w
@@ -141,6 +147,14 @@ struct Shape3 {
   // the cross-wave d core_1 reduction reuses the X regions: one r1 tile row (PNT tiles) per round
   static_assert(kWaves * PNT * 256 <= kWaves * szX, "reduction scratch");
 };
+#ifdef TTX_TEST_HOOKS
+// A/B (test library, ttx_debug_skip bit 18): the same shape with the partial gradients stored as before -- products in the
+// C/D layout, 4-byte non-temporal stores.  A type of its own, so the product library instantiates nothing for it.
+template <class S_>
+struct OldStores : S_ {
+  static constexpr bool W16 = false;
+};
+#endif
 
 // lookup records (+ bag rows) of a wave's groups, one per lane: lane l < LPG*GPW holds record l%LPG of the wave's group
 // l/LPG.  Only the fused-pooling forward still uses this form (one lane per lookup counts its bag's arrival); the operands
@@ -762,6 +776,73 @@ __device__ __forceinline__ void spec_st4(const f32x4& v, float* p) {
   if (NT) __builtin_nontemporal_store(v, (f32x4*)p); else *(f32x4*)p = v;
 }
 
+// How a launch's 16-byte partial-gradient stores (Shape3::W16) leave the backward, chosen per LAUNCH by the host
+// (partial_store_flavour): kernel-uniform, a scalar branch around each of the three store sites.
+//   kStNt  non-temporal: no dirty line left for the end of the kernel, and the rows do not stay on-die either
+//   kStWt  write-through (sc1): no dirty line, and reduce_apply -- the next launch -- finds the rows in the Infinity Cache
+//   kStPl  plain (test library only, for the measurement)
+// b0 / b1 / b2: bytes of pc[0], of ONE chunk's pc[1] slot, of pc[2] -- the write-through stores are buffer stores and are bounds-checked.
+enum { kStNt = 0, kStWt = 1, kStPl = 2 };
+struct PStore {
+  int flav;
+  unsigned b0, b1, b2;
+};
+// float4 `v` to float offset `at` of `base` (rs = the same buffer as a descriptor; FLAV is a constant at every call)
+template <int FLAV>
+__device__ __forceinline__ void st_part4(const f32x4& v, float* __restrict__ base, __amdgpu_buffer_rsrc_t rs, size_t at) {
+  if constexpr (FLAV == kStWt) {
+    __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
+                                           rs, (int)(unsigned)(at * 4), 0, kAuxSc1);
+  } else {
+    spec_st4<FLAV == kStNt>(v, base + at);
+  }
+}
+// the same call under the launch's flavour (CALL names the constant FLAV)
+#define TTX_BY_FLAVOUR(flav, CALL)                                  \
+  do {                                                              \
+    if ((flav) == kStWt) { constexpr int FLAV = kStWt; CALL; }      \
+    else if ((flav) == kStPl) { constexpr int FLAV = kStPl; CALL; } \
+    else { constexpr int FLAV = kStNt; CALL; }                      \
+  } while (0)
+// The three store sites (Shape3::W16), a float4 per lane and store.
+// d core_2 of a group: v[k][h][x4] = values 4*x4 .. +3 of row kk = h*16 + i16 of the partial of the lane's lookup k
+template <class S, int FLAV>
+__device__ __forceinline__ void st_pc2_rows(const f32x4 (&v)[S::LPR][S::HH][S::Q2 / 4], const bool (&live)[S::LPR], const int (&pos2)[S::LPR],
+                                            float* __restrict__ pc2, __amdgpu_buffer_rsrc_t rs) {
+  const int i16 = lane_id() & 15;
+#pragma unroll
+  for (int k = 0; k < S::LPR; ++k)
+    if (live[k]) {
+#pragma unroll
+      for (int h = 0; h < S::HH; ++h)
+#pragma unroll
+        for (int x4 = 0; x4 < S::Q2 / 4; ++x4)
+          st_part4<FLAV>(v[k][h][x4], pc2, rs, (size_t)pos2[k] * S::SL2 + (h * 16 + i16) * S::Q2 + 4 * x4);
+    }
+}
+// d core_0 of a group, transposed accumulators: lane (kq, i16) holds columns y*16 + kq*4 .. +3 of tile row i16 = core-0 row
+// i16 % Q0 of lookup i16 / Q0, whose partial is row `pos` (< 0: no such lookup)
+template <class S, int FLAV>
+__device__ __forceinline__ void st_pc0_rows(const f32x4 (&da)[S::K0T], int pos, float* __restrict__ pc0, __amdgpu_buffer_rsrc_t rs) {
+  const int lane = lane_id(), i16 = lane & 15, kq = lane >> 4;
+  if (pos < 0) return;
+  const size_t at = (size_t)pos * S::SL0 + (i16 % S::Q0) * S::K0 + kq * 4;
+#pragma unroll
+  for (int y = 0; y < S::K0T; ++y) st_part4<FLAV>(da[y], pc0, rs, at + y * 16);
+}
+// the cooperative d core_1 of a pass, transposed accumulators: lane (kq, i16) holds columns kq*4 .. +3 of column tile w*TPW + x,
+// row y*16 + i16 of the chunk's slot
+template <class S, int FLAV>
+__device__ __forceinline__ void st_pc1_tiles(const f32x4 (&acc)[S::K0T][S::TPW], float* __restrict__ pc1, __amdgpu_buffer_rsrc_t rs, int pass,
+                                             int w) {
+  const int lane = lane_id(), i16 = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int y = 0; y < S::K0T; ++y)
+#pragma unroll
+    for (int x = 0; x < S::TPW; ++x)
+      st_part4<FLAV>(acc[y][x], pc1, rs, (size_t)(y * 16 + i16) * S::N1 + pass * S::PW + (w * S::TPW + x) * 16 + kq * 4);
+}
+
 // everything the backward of one (sub-)chunk fetches from global memory, per wave -- issued in one go so that
 // the dependent chain records -> operands is paid once (and, with sub-chunks, one sub-chunk ahead).
 // Lane (quarter kq, i16) works for the LPR lookups kq*LPR + k of a group (the lookups of its four accumulator rows): it reads
@@ -1033,10 +1114,14 @@ template <class S, bool MULTI, bool PAD = false>  // MULTI: a chunk of the plan 
 __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_bwd_kernel(TTX_KHEAD_PARAMS Plan P, CorePtrs C, int B, int p1,
                                                              const int64_t* __restrict__ rowidx,
                                                              const float* __restrict__ d_output,
-                                                             Partials PC, int dbg, long long* stamps, RealDims R) {
+                                                             Partials PC, int dbg, long long* stamps, RealDims R, PStore PS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   TTX_KHEAD_ADOPT(P, C);
   zero_hot_counters(PC);
+  // 16-byte partial stores: d core_0 and the cooperative d core_1 come out transposed.  Not in the sub-chunk walk: its launches hand
+  // over more than the Infinity Cache holds, so they stay non-temporal, and the 16-byte layout alone measured 0.2 % slower there
+  // (cfg5shard 0.5590 / 0.5597 against 0.5570 / 0.5584 ms per step, profiles/partial_stores.md)
+  constexpr bool W16 = S::W16 && !PAD && !MULTI;
   const int chunk = blockIdx.x;
 #define SSTAMP(i) do { if (stamps && threadIdx.x == 0) stamps[(size_t)chunk * 16 + (i)] = wall_clock64(); } while (0)
   SSTAMP(0);
@@ -1059,6 +1144,8 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
   const bool has_row = hdr3 != 0;
   const float* B1 = C.c[1] + (size_t)s * (PAD ? R.sl1 : S::SL1);
   float* pc1 = PC.pc[1] + (size_t)cr.w * (PAD ? R.sl1 : S::SL1);  // .w = the chunk's partial slot
+  // (W16) the partial buffers as descriptors, for the write-through flavour
+  const __amdgpu_buffer_rsrc_t rp0 = make_rsrc(PC.pc[0], PS.b0), rp1 = make_rsrc(pc1, PS.b1), rp2 = make_rsrc(PC.pc[2], PS.b2);
   // A chunk of the plan may hold several sub-chunks of S::MC lookups (large batches: one 16 KB pivot partial
   // per 128 instead of per 16 lookups -- the partials, not the arithmetic, bound the kernel there).  The
   // work-group walks them; the cooperative d core_1 accumulates across sub-chunks in acc2p and is stored once.
@@ -1258,7 +1345,9 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
           }
         }
         }
-        if (pass == S::NP - 1 && !(dbg & 1)) {
+        if constexpr (W16) {  // a lane's Q2 values of row kk are consecutive floats of the partial: whole float4s
+          if (pass == S::NP - 1 && !(dbg & 1)) TTX_BY_FLAVOUR(PS.flav, (st_pc2_rows<S, FLAV>(pc2v[gi], live, cur.pos2[gi], PC.pc[2], rp2)));
+        } else if (pass == S::NP - 1 && !(dbg & 1)) {
 #pragma unroll
           for (int k = 0; k < S::LPR; ++k)
             if (live[k]) {
@@ -1305,6 +1394,15 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
         }
       }
       // ---- d core_0 rows += dX0 * Bs^T: k-step columns {c..c+3} ----
+      if constexpr (W16) {
+        // The transposed product below leaves tile row i16 in lane i16, but the record of that row's lookup sits with the lanes of
+        // quarter (i16 / Q0) / LPR.  The row of its d core_0 partial (-1: no lookup) crosses through LDS: column K0P of the wave's A
+        // tile, row = lookup of the group -- a padding column (LDA >= K0P + 2) nothing else reads or writes.
+        if (pass == S::NP - 1 && i16 == 0) {
+#pragma unroll
+          for (int k = 0; k < S::LPR; ++k) Aw[(kq * S::LPR + k) * S::LDA + S::K0P] = __int_as_float(live[k] ? cur.pos0[gi][k] : -1);
+        }
+      }
       {
         const float* xr = Xw + i16 * S::LD + kq;
         const float* br = Bp + i16 * S::LDB + kq;
@@ -1328,7 +1426,7 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int y = 0; y < S::K0T; ++y) da[gi][y] = mfma4(ac[u], bc[u][y], da[gi][y]);
+            for (int y = 0; y < S::K0T; ++y) da[gi][y] = W16 ? mfma4(bc[u][y], ac[u], da[gi][y]) : mfma4(ac[u], bc[u][y], da[gi][y]);
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             ac[u] = an[u];
@@ -1340,6 +1438,13 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
         }
         TTX_PRIO(0);
         if (gi == 0 && pass == 0) SSTAMP(5);
+        if constexpr (W16) {
+          // transposed: this lane holds tile row i16 = (lookup i16 / Q0, core-0 row i16 % Q0), columns y*16 + kq*4 .. +3
+          if (pass == S::NP - 1 && !(dbg & 1)) {
+            const int p0 = __float_as_int(Aw[(i16 / S::Q0) * S::LDA + S::K0P]);
+            TTX_BY_FLAVOUR(PS.flav, (st_pc0_rows<S, FLAV>(da[gi], p0, PC.pc[0], rp0)));
+          }
+        } else
         // rows kq*4 + r = (lookup kq*LPR + r / Q0, core-0 row r % Q0); columns y*16 + i16
         if (pass == S::NP - 1 && !(dbg & 1)) {
 #pragma unroll
@@ -1385,14 +1490,17 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
 #pragma unroll
           for (int y = 0; y < S::K0T; ++y)
 #pragma unroll
-            for (int x = 0; x < S::TPW; ++x) acc2[y][x] = mfma4(avv[y], bv[x], acc2[y][x]);
+            for (int x = 0; x < S::TPW; ++x) acc2[y][x] = W16 ? mfma4(bv[x], avv[y], acc2[y][x]) : mfma4(avv[y], bv[x], acc2[y][x]);
         }
       }
+      // (W16: transposed -- row (= core_1 row k0) = y*16 + i16, columns tile*16 + kq*4 .. +3)
       if constexpr (MULTI) {  // carried across the sub-chunks, stored once at the end
 #pragma unroll
         for (int y = 0; y < S::K0T; ++y)
 #pragma unroll
           for (int x = 0; x < S::TPW; ++x) acc2p[pass][y][x] += acc2[y][x];
+      } else if constexpr (W16) {
+        if (!(dbg & 128)) TTX_BY_FLAVOUR(PS.flav, (st_pc1_tiles<S, FLAV>(acc2, pc1, rp1, pass, w)));
       } else if (!(dbg & 128)) {  // single sub-chunk: this pass's block is final
 #pragma unroll
         for (int y = 0; y < S::K0T; ++y)
@@ -1425,6 +1533,12 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
 #undef c2
   } while (MULTI && ++sc < nsub);  // sub-chunks
   if constexpr (S::COOP && MULTI) {
+    if constexpr (W16) {
+      if (!(dbg & 4)) {
+#pragma unroll
+        for (int pass = 0; pass < S::NP; ++pass) TTX_BY_FLAVOUR(PS.flav, (st_pc1_tiles<S, FLAV>(acc2p[pass], pc1, rp1, pass, w)));
+      }
+    } else
     // C/D layout: row (= core_1 row k0) = y*16 + kq*4 + r, column = tile*16 + i16
     if (!(dbg & 4)) {
 #pragma unroll
@@ -1521,9 +1635,31 @@ static int spec_launch_fwd_v(const Plan& P, const CorePtrs& C, float* rows, floa
   return TTX_OK;
 }
 
+// Flavour of a launch's 16-byte partial stores (Shape3::W16), by the upper bound of the bytes it hands to reduce_apply.
+// Write-through keeps them in the 256 MiB Infinity Cache for the next launch; past kPartialWtBytes they go non-temporal as before.
+// Measured (profiles/partial_stores.md; rocprofv3 averages in us, non-temporal -> write-through, q = [4,4,4], ranks 32):
+//   partial bytes (bound)          backward            reduce_apply
+//   cfg2        10k lookups   23 MiB    16.02 ->  15.95      9.63 ->  7.82   wins 1.9 us
+//   cfg5shard1  82k lookups  163 MiB    88.97 ->  91.04     34.57 -> 27.62   wins 4.9 us
+//   cfg5shard  328k lookups  414 MiB   316.36 -> 315.91     83.13 -> 87.04   loses 3.5 us: they no longer fit
+// Nothing was measured between 163 and 414 MiB; the switch sits at three quarters of the cache, above the largest measured win.
+constexpr long long kPartialWtBytes = 192ll << 20;
+// (test library: g_partial_flavour = 1 + a flavour forced for every launch, g_old_stores = OldStores<S>; ttx_tt_common.h)
+template <class S>
+static PStore partial_store_flavour(const Plan& P, long long nnz) {
+  const long long b0 = nnz * S::SL0 * 4, b1 = (long long)S::SL1 * 4, b2 = nnz * S::SL2 * 4;
+  PStore ps;
+  ps.flav = b0 + b2 + (long long)P.max_chunks * b1 <= kPartialWtBytes ? kStWt : kStNt;
+  if (g_partial_flavour) ps.flav = g_partial_flavour - 1;
+  // (the write-through stores address with 32-bit byte offsets into bounds-checked descriptors)
+  if (b0 > 0xffffffffll || b2 > 0xffffffffll) ps.flav = kStNt;
+  ps.b0 = (unsigned)(b0 > 0xffffffffll ? 0 : b0); ps.b1 = (unsigned)b1; ps.b2 = (unsigned)(b2 > 0xffffffffll ? 0 : b2);
+  return ps;
+}
+
 template <class S, bool MULTI, bool PAD = false>
 static int spec_launch_bwd_v(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx,
-                             const float* d_output, const Partials& PC, const RealDims& R, hipStream_t st) {
+                             const float* d_output, const Partials& PC, const RealDims& R, long long nnz, hipStream_t st) {
   size_t lds = S::lds_floats_bwd * sizeof(float);
   // (debug: TTX_DEBUG_BWD_LDS=<bytes> asks for more LDS than the kernel uses -- fewer work-groups per CU, to time a work-group's
   //  own critical path without its neighbours, scripts/phase_times_large.py)
@@ -1536,9 +1672,20 @@ static int spec_launch_bwd_v(const Dims& d, const Plan& P, const CorePtrs& C, in
   RealDims Rv = R;
   if ((((uintptr_t)C.c[0]) | ((uintptr_t)C.c[1]) | ((uintptr_t)C.c[2]) | ((uintptr_t)d_output) | ((uintptr_t)PC.pc[2])) & 15) Rv.v4 = 0;
   hipLaunchKernelGGL((spec_bwd_kernel<S, MULTI, PAD>), dim3(P.max_chunks), dim3(kThreads), lds, st, TTX_KHEAD_ARGS(P, C) P, C, B, d.p[1], rowidx,
-                     d_output, PC, g_debug_skip, g_stamps, Rv);
+                     d_output, PC, g_debug_skip, g_stamps, Rv, partial_store_flavour<S>(P, nnz));
   TTX_HIP(hipGetLastError());
   return TTX_OK;
+}
+// exact shapes: the kernel with 16-byte partial stores, or (test library, g_old_stores) the one with the stores as they were
+template <class S, bool MULTI>
+static int spec_launch_bwd_x(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx,
+                             const float* d_output, const Partials& PC, const RealDims& R, long long nnz, hipStream_t st) {
+#ifdef TTX_TEST_HOOKS
+  if constexpr (S::W16 && !MULTI) {  // (the sub-chunk walk stores as before either way)
+    if (g_old_stores) return spec_launch_bwd_v<OldStores<S>, MULTI>(d, P, C, B, rowidx, d_output, PC, R, nnz, st);
+  }
+#endif
+  return spec_launch_bwd_v<S, MULTI>(d, P, C, B, rowidx, d_output, PC, R, nnz, st);
 }
 
 // P.MC > S::MC: the plan's chunks hold several sub-chunks (only shapes with S::SUB are ever planned that way)
@@ -1567,14 +1714,14 @@ static int spec_launch_fwd(const Plan& P, const CorePtrs& C, float* rows, float*
 
 template <class S>
 static int spec_launch_bwd(const Dims& d, const Plan& P, const CorePtrs& C, int B, const int64_t* rowidx,
-                           const float* d_output, const Partials& PC, bool pad, const RealDims& R, hipStream_t st) {
+                           const float* d_output, const Partials& PC, bool pad, const RealDims& R, long long nnz, hipStream_t st) {
   if constexpr (S::SUB) {
     if (P.MC > S::MC)
-      return pad ? spec_launch_bwd_v<S, true, true>(d, P, C, B, rowidx, d_output, PC, R, st)
-                 : spec_launch_bwd_v<S, true>(d, P, C, B, rowidx, d_output, PC, R, st);
+      return pad ? spec_launch_bwd_v<S, true, true>(d, P, C, B, rowidx, d_output, PC, R, nnz, st)
+                 : spec_launch_bwd_x<S, true>(d, P, C, B, rowidx, d_output, PC, R, nnz, st);
   }
-  return pad ? spec_launch_bwd_v<S, false, true>(d, P, C, B, rowidx, d_output, PC, R, st)
-             : spec_launch_bwd_v<S, false>(d, P, C, B, rowidx, d_output, PC, R, st);
+  return pad ? spec_launch_bwd_v<S, false, true>(d, P, C, B, rowidx, d_output, PC, R, nnz, st)
+             : spec_launch_bwd_x<S, false>(d, P, C, B, rowidx, d_output, PC, R, nnz, st);
 }
 
 // the benchmark shape: two column passes, 16 lookups per chunk (one M-tile per wave).  Measured against
@@ -1668,7 +1815,7 @@ constexpr int kSpecNotMine = -0x5bec;  // the id belongs to another family's tra
       bool pad, const RealDims &R, hipStream_t st
 #define TTX_SPEC_BWD_ARGS                                                                                             \
   SpecId id, const Dims &d, const Plan &P, const CorePtrs &C, int B, const int64_t *rowidx, const float *d_output,        \
-      const Partials &PC, bool pad, const RealDims &R, hipStream_t st
+      const Partials &PC, bool pad, const RealDims &R, long long nnz, hipStream_t st
 #define TTX_SPEC_DECLARE(G)         \
   int spec_fwd_##G(TTX_SPEC_FWD_ARGS); \
   int spec_bwd_##G(TTX_SPEC_BWD_ARGS);
@@ -1679,7 +1826,7 @@ TTX_SPEC_DECLARE(128a)
 TTX_SPEC_DECLARE(128b)
 TTX_SPEC_DECLARE(128c)
 #define TTX_SPEC_CALLF(S) spec_launch_fwd<S>(P, C, rows, zout, nzero, F, fused, pad, R, st)
-#define TTX_SPEC_CALLB(S) spec_launch_bwd<S>(d, P, C, B, rowidx, d_output, PC, pad, R, st)
+#define TTX_SPEC_CALLB(S) spec_launch_bwd<S>(d, P, C, B, rowidx, d_output, PC, pad, R, nnz, st)
 #define TTX_SPEC_DEFINE(G)                                                                 \
   int spec_fwd_##G(TTX_SPEC_FWD_ARGS) {                                                    \
     switch (id) { TTX_SPEC_CASES_##G(TTX_SPEC_CALLF) default: break; }                     \

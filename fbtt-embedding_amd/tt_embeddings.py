@@ -1381,8 +1381,9 @@ def debug_lds_budget(nbytes: int) -> None:
 def debug_skip(mask: int) -> None:
     """bit 8: force the generic kernels; bit 15: exact-shape templates only; bit 16: reduce_apply with a work-group (not a wave) per
     small slice; bit 17: plans list the pivot's chunks in slot order (one column) instead of dealing them over 8 columns, one per
-    XCD -- these four leave the results valid; the other bits skip kernel phases / launches (results INVALID).  0 = normal
-    operation."""
+    XCD; bit 18: the shape-specialised backward stores its partial gradients as 4-byte non-temporal stores, as before the 16-byte
+    ones; bits 19..20: the flavour of the 16-byte partial stores forced for every launch (1 non-temporal, 2 write-through, 3 plain)
+    -- these leave the results valid; the other bits skip kernel phases / launches (results INVALID).  0 = normal operation."""
     _check(hooks_lib().ttx_debug_skip(int(mask)))
     _knobs_changed()
 

@@ -24,7 +24,10 @@ int ttx_debug_lds_budget(int32_t bytes);
  * bit 15 shape-specialised kernels for exact shapes only; bit 16 reduce_apply with a work-group per small slice instead of a wave
  * per slice (round 6; results stay valid up to the order of addition); bit 17 plans built while it is set list the pivot's chunks
  * in slot order (one column) instead of dealing the slots column-major over 8 columns, one per XCD (the order is
- * performance only: results stay bit-identical).  0 = normal operation. */
+ * performance only: results stay bit-identical); bit 18 the shape-specialised backward stores its partial gradients as 4-byte
+ * non-temporal stores from products in the C/D layout, as before the 16-byte stores (results stay bit-identical);
+ * bits 19..20 force the flavour of the 16-byte partial stores for every launch: 1 non-temporal, 2 write-through, 3 plain (timing
+ * only: results stay bit-identical).  0 = normal operation. */
 int ttx_debug_skip(int32_t mask);
 /* A/B knob (scripts/bench_cache.py): 1 = ttx_cache_forward uses the one-group-per-lookup kernel for every D */
 int ttx_debug_cache_fwd(int32_t lookup_groups);

@@ -66,6 +66,32 @@ def parse_asm(path):
     return kernels
 
 
+def vmem_stores(path):
+    """{mangled name: [(bits, modifiers, results)]} -- every vector store to global memory of every kernel body, in listing order:
+    its width in bits, its cache-policy modifiers (a set out of nt / sc0 / sc1) and whether it stands behind the kernel's first
+    MFMA, i.e. can be a store of results (tests/test_partial_stores_cpu.py)"""
+    width = {"byte": 8, "short": 16, "dword": 32, "dwordx2": 64, "dwordx3": 96, "dwordx4": 128}
+    kernels, cur, seen_mfma = {}, None, False
+    for raw in open(path):
+        line = raw.strip()
+        m = re.match(r"^(_Z\w+):\s*(;.*)?$", line)
+        if m:
+            cur, seen_mfma = kernels.setdefault(m.group(1), []), False
+            continue
+        if line.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        if cur is None or not line or line[0] in ".;" or line.endswith(":"):
+            continue
+        ins = line.split(";")[0].strip()
+        if ins.startswith("v_mfma"):
+            seen_mfma = True
+        m = re.match(r"^(?:global|buffer|flat)_store_(\w+)\s", ins)
+        if m:
+            cur.append((width.get(m.group(1).split("_")[0], 0), set(re.findall(r"\b(nt|sc0|sc1)\b", ins)), seen_mfma))
+    return kernels
+
+
 def parse_res(path):
     res, cur = {}, None
     for line in open(path):
