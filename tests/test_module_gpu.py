@@ -1270,6 +1270,75 @@ def test_first_factor_beyond_four_runs_as_part_lookups(q, ranks, tables):
         assert_adagrad_close(ms.tt_cores[k].detach().cpu().numpy(), cores[k], ref_g[k], f"split q={q} adagrad core{k}")
 
 
+def test_part_lookups_on_the_sub_chunk_walk():
+    """q = [8, 8, 8], ranks [32, 32] (the reference's default factoring of D = 512): two part lookups per index on the q = [4, 8, 8]
+    template, the one whose sub-chunk walk re-stages its core-1 block in every pass (tests/test_spec_walk_gpu.py).  The part
+    lookups double the lookup count the chunk length is chosen for; ttx_set_chunk(64) (test library) asks for the walk at 150
+    indices.  The knob reaches the ctypes nodes only -- the bag module's part lookups go through the C++ node, which is linked to
+    the product library -- so the case runs on TTEmbedding, whose part lookups are TTRowsLookupFunction's (the same under both
+    settings of this file's `node`).  Forward, dense gradients, fused SGD and Adagrad against float64 (tests/tt_ref64.py)."""
+    import spec_ref as SR
+    import tt_embeddings as E
+    import tt_embeddings_ops as ops
+    import tt_ref64 as R64
+    from util import ATOL_SCALE, RTOL
+
+    p, q, ranks = [5, 6, 7], [8, 8, 8], [32, 32]
+    r = [1] + ranks + [1]
+    E_, D, N = int(np.prod(p)), int(np.prod(q)), 150
+    rs = np.random.RandomState(91)
+    idx = rs.randint(0, E_, size=(3, N // 3)).astype(np.int64)
+    d_out = (rs.rand(3, N // 3, D) * 0.1).astype(np.float32)
+    cores = G.make_cores(92, 1, p, q, r, "signed")
+    ar, tb = np.arange(N, dtype=np.int64), np.zeros(N, np.int64)
+    ref = R64.forward_backward(1, p, q, r, N, idx.reshape(-1), ar, tb, cores, d_out=d_out.reshape(1, N, D))
+    g = O.make_geom(1, p, q, r)
+    o_out = O.tt_forward(g, N, D, idx.reshape(-1), ar, tb, cores)
+    o_g = O.tt_backward(g, O.OPTIM_DENSE, N, D, 0, 0, idx.reshape(-1), ar, tb, d_out.reshape(1, N, D), [x.copy() for x in cores])
+    split_p, split_q = [2 * p[0], p[1], p[2]], [4, 8, 8]
+    assert SR.spec_match(split_q, ranks) == ("S_32_8_32_8", False) and SR.spec_mc(split_q, ranks, 2 * N, knob64=True) == 64
+
+    def close64(got, want, oracle, what):
+        f, u = R64.widen_factor(oracle, want)
+        print(f"[part-lookups walk] {what}: {R64.default_units(got, want):.3f} default bounds from float64 (the fp32 oracle: {u:.3f}, bound x{f:.2f})")
+        assert_close(got, want, what, rtol=RTOL * f, atol_scale=ATOL_SCALE * f)
+        return f
+
+    def module(**kw):
+        m = ops.TTEmbedding(E_, D, ranks, p, q, weight_dist="uniform", device=DEV, **kw)
+        assert m._split0 == 2, "the geometry is expected to split"
+        with torch.no_grad():
+            for dst, src in zip(m.tt_cores, cores):
+                dst.copy_(t(src))
+        return m
+
+    E.set_chunk(64)
+    try:
+        z = torch.zeros(2 * N, dtype=torch.int64, device=DEV)
+        plan = E.make_plan(1, split_p, split_q, r, 2 * N, z, z)
+        torch.cuda.synchronize()
+        assert int(plan.buf[:8].view(torch.int32)[1]) == 64, "the part lookups' plan: four sub-chunks of 16 lookups per chunk"
+        m = module(sparse=False)
+        out = m(t(idx))
+        out.backward(t(d_out))
+        close64(out.detach().cpu().numpy().reshape(1, N, D), ref["out"], o_out, "out")
+        fg = [close64(m.tt_cores[k].grad.cpu().numpy(), ref["grads"][k], o_g[k], f"grad{k}") for k in range(3)]
+        m = module(sparse=True, optimizer=ops.OptimType.SGD, learning_rate=LR)
+        m(t(idx)).backward(t(d_out))
+        want = R64.sgd_step(cores, ref["grads"], LR)
+        for k in range(3):
+            close64(m.tt_cores[k].detach().cpu().numpy(), want[k], cores[k] - np.float32(LR) * o_g[k], f"sgd core{k}")
+        m = module(sparse=True, optimizer=ops.OptimType.EXACT_ADAGRAD, learning_rate=LR, eps=EPS)
+        m(t(idx)).backward(t(d_out))
+        e_w, e_s = R64.adagrad_step(cores, [np.zeros_like(x) for x in cores], ref["grads"], ref["touched"], LR, EPS)
+        for k in range(3):
+            R64.assert_state_close(m.optimizer_state[k].cpu().numpy(), e_s[k], ref["grads"][k], f"adagrad state{k}", scale=fg[k])
+            assert_adagrad_close(m.tt_cores[k].detach().cpu().numpy(), e_w[k], ref["grads"][k], f"adagrad core{k}", lr=LR, eps=EPS,
+                                 scale=fg[k])
+    finally:
+        E.set_chunk(0)
+
+
 @pytest.mark.parametrize("optimizer", ["SGD", "EXACT_ADAGRAD"])
 def test_padded_first_factor_over_several_steps(node, optimizer):
     """q = [5, 8, 8] (the reference's default factoring of D = 320): the part lookups run on a zero-padded copy of core 0 (and of

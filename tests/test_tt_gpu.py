@@ -331,13 +331,19 @@ def test_hot_slices_are_reduced_by_several_work_groups(p, q, r):
                 assert_adagrad_close(got["cores"][k], orc["cores"][k], gref[k], f"hot {p} adagrad core{k}")
 
 
-@pytest.mark.parametrize("q", [[4, 4, 4], [2, 4, 4]])
+@pytest.mark.parametrize("q", [[4, 4, 4], [2, 4, 4], [4, 8, 8]])
 def test_benchmark_shape_large_batch_variant(q):
     """the benchmark shape (and its q0 = 2 sibling) at a batch that no longer fits the single-launch plan
-    (> 16384 lookups): forward, dense gradients and fused SGD against the oracle"""
+    (> 16384 lookups): forward, dense gradients and fused SGD against the oracle.  q = [4, 8, 8] (the reference's default
+    factoring of D = 256): the one template whose sub-chunk walk re-stages its core-1 block in every column pass of every
+    sub-chunk (Shape3::B1ONCE false, tests/test_spec_walk_gpu.py) -- here through the product library's own threshold, no knob"""
     p, r = [9, 8, 7], [1, 32, 32, 1]
     E_, D, B = int(np.prod(p)), int(np.prod(q)), 6800
     idx, off = G.make_bags(51, B, E_, 20, 2, 1)
+    import tt_embeddings as E
+
+    E._knobs_changed()  # (an earlier test's last call may have gone to the test library: back to the product one)
+    assert E.lib() is E._product and E.lib().ttx_debug_state() == 0, "the product library, at its own settings"
     assert idx.size > 131072  # ... and the plan's chunks hold four 16- / 32-lookup sub-chunks (kernel variant MULTI)
     c = dict(tables=1, T=3, p=p, q=q, r=r, B=B, D=D, indices=idx, offsets=off,
              cores=G.make_cores(52, 1, p, q, r, "signed"), d_out=G.make_grad(53, 1, B, D))
