@@ -1153,6 +1153,297 @@ __global__ __launch_bounds__(kReduceThreads, TTX_REDUCE_WAVES) void reduce_apply
   }
 }
 
+// ---------------- small launches: owners that make one trip to memory ----------------
+// At a few thousand lookups over thin slices of at most 32 float4 lanes reduce_apply_kernel's owners are trips to memory, not
+// bytes: a thin owner (eight waves) puts cnt / 8 row groups to work with four rows in flight each -- three dependent trips for
+// the 46 rows of a slice at the benchmark batch -- and a pivot owner takes its two float4 columns per thread one after the
+// other.  Here an owner work-group is either two thin slices (four waves each) or 512 float4 columns of one pivot slice.
+// Half-wave h of a thin slice's eight sums rows h, h + 8, .. of its float4 column with NF requests in flight -- 64 rows of the
+// slice in ONE trip --, the eight sums are added in their order through LDS behind one barrier; a pivot thread sums its
+// column's chunk partials in index order, all of them (up to NF) in one trip.  HOT slices (a skewed stream) are not the
+// owners': behind them the grid holds the segment work-groups of the thin cores and the column work-groups of the pivot, the
+// same partition, thresholds, scratch buffers and arrival protocol as reduce_apply_kernel's, restated with scalar arguments (a
+// segment's rows and a slice's segment sums are summed by sixteen half-waves and folded in their order: sum_rows4's deep loops
+// inlined here spill 40 bytes per lane); in a launch without hot slices they read the plan's hot count and leave.  No run-time subscript of an argument: zero
+// scratch at three work-groups per CU (tests/test_reduce_small_cpu.py).  The host picks this kernel by the launch's shape
+// (small_route).  Deterministic: fixed partition, fixed order.
+// (Measured at the benchmark batch, profiles/reduce_small.md: a slice per half-wave -- six trips -- +1.6 us per step over
+//  reduce_apply_kernel, a wave per slice neutral, four and eight half-waves -1.0 us, sixteen -0.6 us; thin work-groups dealt
+//  among the pivot blocks +0.6 us against thin work-groups first.)
+#ifndef TTX_RS_NF
+#define TTX_RS_NF 8      // rows in flight per lane
+#endif
+#ifndef TTX_RS_PIVOT_COLS
+#define TTX_RS_PIVOT_COLS 1  // float4 columns of a pivot slice per thread, one after the other (A/B: 2 = as reduce_apply_kernel's owner)
+#endif
+#ifndef TTX_RS_WAVES
+#define TTX_RS_WAVES 6   // waves per SIMD the register allocation leaves room for: three 512-thread work-groups per CU (at 8 it spills)
+#endif
+constexpr int kSmallThreads = 512;
+constexpr int kSmallHalves = kSmallThreads / 32;                  // half-waves of a work-group
+constexpr int kThinHalves = 8;                                    // half-waves per thin slice
+constexpr int kSmallSlices = kSmallHalves / kThinHalves;          // thin slices of a work-group
+constexpr int kSmallPivotCols = kSmallThreads * TTX_RS_PIVOT_COLS;  // float4 columns of a pivot block
+constexpr int kSmallBlockRows = 256;                              // rows per block sum of an owner that keeps a long slice
+constexpr long long kSmallMaxRows = 64 * kSegThin;                // lookups beyond which a launch takes reduce_apply_kernel
+struct SmallRA {  // (scalars only: a run-time subscript into a by-value argument sends it through scratch memory, sel_core)
+  float *w0, *w1, *w2, *s0, *s1, *s2, *g0, *g1, *g2;  // cores, Adagrad state, dense gradient (NULL where the optimizer has none)
+  float *seg0, *seg2;  // segment sums of the thin cores' hot slices (Partials::seg)
+  int* hot_cnt;        // arrival counters, one per core slice (Partials::hot_cnt)
+  int S0, S1, S2;      // slices per core
+  int V0, V1, V2;      // float4 lanes per slice
+  int nthin, npiv, hp;  // thin owner work-groups, pivot owner blocks, blocks per pivot slice
+  int nseg;            // segment work-groups per thin core; the pivot's column work-groups are the rest of the grid
+  int optim;
+  float lr, eps;
+};
+
+__device__ __forceinline__ void add4(float4& a, const float4 x) { a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w; }
+
+// rows i, i + stride, .. < end of one float4 column (row r at col[r V]), NF requests in flight, block sums of
+// kSmallBlockRows / NF rounds into the total: up to that many rounds the plain running sum
+template <int NF>
+__device__ __forceinline__ float4 small_sum(const float4* __restrict__ col, int V, int i, int end, int stride) {
+  float4 tot = make_float4(0.f, 0.f, 0.f, 0.f), acc = tot;
+  int rounds = 0;
+  for (; i + (NF - 1) * stride < end; i += NF * stride) {
+    float4 x[NF];
+#pragma unroll
+    for (int u = 0; u < NF; ++u) x[u] = col[(size_t)(i + u * stride) * V];
+#pragma unroll
+    for (int u = 0; u < NF; ++u) add4(acc, x[u]);
+    if (++rounds == kSmallBlockRows / NF) {
+      add4(tot, acc);
+      acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      rounds = 0;
+    }
+  }
+  if (i < end) {  // the last round: requests behind the end read row i again and are not added
+    float4 x[NF - 1];
+#pragma unroll
+    for (int u = 0; u < NF - 1; ++u) x[u] = col[(size_t)(i + u * stride < end ? i + u * stride : i) * V];
+#pragma unroll
+    for (int u = 0; u < NF - 1; ++u)
+      if (i + u * stride < end) add4(acc, x[u]);
+  }
+  add4(tot, acc);
+  return tot;
+}
+
+struct ThinSlice {
+  const int* off;
+  const float4* pc;
+  float *w, *s, *g;
+  int V, idx;
+};
+// thin slice number n of the launch: core 0's slices, then core 2's
+__device__ __forceinline__ ThinSlice thin_slice(int n, const int* off0, const int* off2, const float* pc0, const float* pc2,
+                                                const SmallRA& A) {
+  const bool c2 = n >= A.S0;
+  ThinSlice T;
+  T.idx = c2 ? n - A.S0 : n;
+  T.off = c2 ? off2 : off0;
+  T.pc = (const float4*)(c2 ? pc2 : pc0);
+  T.w = c2 ? A.w2 : A.w0;
+  T.s = c2 ? A.s2 : A.s0;
+  T.g = c2 ? A.g2 : A.g0;
+  T.V = c2 ? A.V2 : A.V0;
+  return T;
+}
+
+// grid: [thin owners | pivot owners | segment work-groups of core 0, of core 2 | column work-groups of the pivot]
+__global__ __launch_bounds__(kSmallThreads, TTX_RS_WAVES) void reduce_apply_small_kernel(
+    const int* __restrict__ off0, const int* __restrict__ offp, const int* __restrict__ off2, const int* __restrict__ hdr,
+    const float* __restrict__ pc0, const float* __restrict__ pc1, const float* __restrict__ pc2, SmallRA A) {
+  __shared__ __attribute__((aligned(16))) float4 red[kSmallThreads];
+  __shared__ int s_hot[kSmallThreads];
+  __shared__ int s_last, s_nhot;
+  const int tid = threadIdx.x, nthreads = kSmallThreads;
+  int b = blockIdx.x;
+  if (b < A.nthin) {
+    // ---------------- thin owners: two slices, eight half-waves each ----------------
+    const int hw = tid >> 5, v = tid & 31;
+    const int slot = hw / kThinHalves, h = hw % kThinHalves;
+    const int nthin = A.S0 + A.S2, n = b * kSmallSlices + slot;
+    const ThinSlice T = thin_slice(n < nthin ? n : 0, off0, off2, pc0, pc2, A);
+    const int beg = T.off[T.idx], end = n < nthin ? T.off[T.idx + 1] : beg;
+    const size_t base = (size_t)T.idx * T.V * 4;
+    const bool hot = end - beg > 2 * kSegThin;  // (the segment work-groups own it)
+    const bool act = beg < end && !hot && v < T.V;
+    const ApplyEmit ap{A.optim, A.lr, A.eps, T.w + base, T.s ? T.s + base : nullptr, T.g ? T.g + base : nullptr};
+    ApplyEmit::Pre pre{};
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (beg == end && n < nthin && A.optim == TTX_OPTIM_DENSE && h == 0 && v < T.V)
+      ((float4*)(T.g + base))[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (act) {
+      if (h == 0) pre = ap.prefetch(v);
+      acc = small_sum<TTX_RS_NF>(T.pc + v, T.V, beg + h, end, kThinHalves);
+      if (h != 0) red[tid] = acc;
+    }
+    __syncthreads();
+    if (act && h == 0) {  // half-wave 0 adds the others' sums in their order
+      for (int j = 1; j < kThinHalves; ++j) add4(acc, red[tid + j * 32]);
+      ap(v, acc, pre);
+    }
+    return;
+  }
+  b -= A.nthin;
+  if (b < A.npiv) {
+    // ---------------- pivot owners: float4 columns [hb C, (hb + 1) C) of slice s, C = kSmallPivotCols ----------------
+    const int s = (unsigned)b / (unsigned)A.hp, hb = b - s * A.hp;
+    const int beg = offp[s], end = offp[s + 1];
+    const size_t base = (size_t)s * A.V1 * 4;
+    // hot: the column work-groups own it, unless the pivot has too many hot slices for the column split (reduce_apply_kernel)
+    if (end - beg > kHotRowsPivot && !(hdr[8 + 1] > kMaxHotPivot)) return;
+    const ApplyEmit ap{A.optim, A.lr, A.eps, A.w1 + base, A.s1 ? A.s1 + base : nullptr, A.g1 ? A.g1 + base : nullptr};
+#pragma unroll
+    for (int c = 0; c < TTX_RS_PIVOT_COLS; ++c) {
+      const int v = hb * kSmallPivotCols + c * kSmallThreads + tid;
+      if (v >= A.V1) return;
+      if (beg == end) {
+        if (A.optim == TTX_OPTIM_DENSE) ((float4*)(A.g1 + base))[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+      const ApplyEmit::Pre pre = ap.prefetch(v);
+      ap(v, small_sum<TTX_RS_NF>((const float4*)pc1 + v, A.V1, beg, end, 1), pre);
+    }
+    return;
+  }
+  b -= A.npiv;
+  if (b < 2 * A.nseg) {
+    // ---------------- segment work-group j of a thin core: its share of the hot slice(s) it intersects ----------------
+    const bool c2 = b >= A.nseg;
+    const int j = c2 ? b - A.nseg : b;
+    if (hdr[c2 ? 8 + 2 : 8] == 0) return;  // the plan found no hot slice in this core (-1: it did not look)
+    const int SEG = kSegThin, sl = (c2 ? A.V2 : A.V0) * 4, St_ = c2 ? A.S2 : A.S0;
+    const int hw = tid >> 5, v = tid & 31, V = sl / 4;
+    const int total = hdr[2];
+    const int p0 = j * SEG, p1 = min(p0 + SEG, total);
+    if (p0 >= total) return;
+    const int* const goff = c2 ? off2 : off0;
+    const int* off = goff;
+    int* soff = (int*)red;  // the offset table in LDS when it fits: one coalesced round
+    const bool in_lds = St_ + 1 <= (int)(nthreads * sizeof(float4) / sizeof(int));
+    if (in_lds) {
+      for (int e = tid; e <= St_; e += nthreads) soff[e] = goff[e];
+      __syncthreads();
+      off = soff;
+    }
+    int lo = 0, hi = St_;  // slice containing position p0: the last s with off[s] <= p0
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (off[mid] <= p0) lo = mid; else hi = mid;
+    }
+    bool any_hot = false;  // (work-group-uniform: every thread scans the same few slices)
+    for (int s = lo; s < St_ && off[s] < p1; ++s) any_hot |= (off[s + 1] - off[s] > 2 * SEG);
+    if (!any_hot) return;
+    if (in_lds) {  // `red` is about to be used by the reductions: back to the global table
+      __syncthreads();
+      off = goff;
+    }
+    const float* __restrict__ pc = c2 ? pc2 : pc0;
+    float* const seg = c2 ? A.seg2 : A.seg0;
+    float* const wt = c2 ? A.w2 : A.w0;
+    float* const stt = c2 ? A.s2 : A.s0;
+    float* const dw = c2 ? A.g2 : A.g0;
+    for (int s = lo; s < St_; ++s) {  // at most two hot slices can touch one segment
+      const int sbeg = off[s], send = off[s + 1];
+      if (sbeg >= p1) break;
+      if (send - sbeg <= 2 * SEG) continue;  // not hot: its owner does everything
+      const int beg = max(sbeg, p0), end = min(send, p1);
+      const int slot = (sbeg > p0) ? 1 : 0;
+      {  // the segment's rows of the slice: half-wave hw sums rows hw, hw + 16, .., half-wave 0 adds the sixteen sums in order
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v < V) {
+          acc = small_sum<TTX_RS_NF>((const float4*)pc + v, V, beg + hw, end, kSmallHalves);
+          if (hw != 0) red[tid] = acc;
+        }
+        __syncthreads();
+        if (hw == 0 && v < V) {
+          for (int q = 1; q < kSmallHalves; ++q) add4(acc, red[q * 32 + v]);
+          ((float4*)(seg + (size_t)(2 * j + slot) * sl))[v] = acc;
+        }
+      }
+      // arrival, as in reduce_apply_kernel: the stores are complete at the barrier, ONE lane releases at agent scope and counts
+      // the work-group in; the work-group that completes the count acquires and folds the segment sums in segment order
+      __syncthreads();
+      const int j_first = sbeg / SEG, j_last = (send - 1) / SEG;
+      if (tid == 0) {
+        const int idx = s + (c2 ? A.S0 + A.S1 : 0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const int old = __hip_atomic_fetch_add(&A.hot_cnt[idx], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (old == j_last - j_first);
+        if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      }
+      __syncthreads();
+      if (s_last) {  // (work-group-uniform) the slice's segment sums, in segment order within a half-wave, the half-waves in order
+        const size_t base = (size_t)s * sl;
+        const ApplyEmit ap{A.optim, A.lr, A.eps, wt + base, stt ? stt + base : nullptr, dw ? dw + base : nullptr};
+        const SegRow row{j_first, sbeg > j_first * SEG ? 1 : 0};
+        ApplyEmit::Pre pre{};
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v < V) {
+          if (hw == 0) pre = ap.prefetch(v);
+          for (int i = hw; i <= j_last - j_first; i += kSmallHalves) add4(acc, ((const float4*)seg)[row(i) * V + v]);
+          if (hw != 0) red[tid] = acc;
+        }
+        __syncthreads();
+        if (hw == 0 && v < V) {
+          for (int q = 1; q < kSmallHalves; ++q) add4(acc, red[q * 32 + v]);
+          ap(v, acc, pre);
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  b -= 2 * A.nseg;
+  // ---------------- column work-group b of the pivot: float4 columns [b C, (b + 1) C) of EVERY hot slice ----------------
+  const int nhp = hdr[8 + 1];
+  if (nhp == 0 || nhp > kMaxHotPivot) return;  // none, or too many for the column split: they stay with their owners
+  const int V = A.V1, sl = V * 4, C = kHotColsPivot;
+  const int c0 = b * C, c1 = min(V, c0 + C);
+  if (c0 >= c1) return;
+  const int G = nthreads / C, g = tid / C, v = c0 + (tid - g * C);
+  const bool act = g < G && v < c1;
+  for (int s0 = 0; s0 < A.S1; s0 += nthreads) {  // (work-group-uniform control flow throughout)
+    if (tid == 0) s_nhot = 0;
+    __syncthreads();
+    const int sidx = s0 + tid;
+    if (sidx < A.S1 && offp[sidx + 1] - offp[sidx] > kHotRowsPivot) s_hot[atomicAdd(&s_nhot, 1)] = sidx;
+    __syncthreads();
+    const int nh = s_nhot;
+    for (int hh = 0; hh < nh; ++hh) {  // (the order in which a work-group takes its hot slices does not matter)
+      const int sh = s_hot[hh];
+      const int beg = offp[sh], end = offp[sh + 1];
+      const size_t base = (size_t)sh * sl;
+      const ApplyEmit ap{A.optim, A.lr, A.eps, A.w1 + base, A.s1 ? A.s1 + base : nullptr, A.g1 ? A.g1 + base : nullptr};
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      ApplyEmit::Pre pre{};
+      if (act && g == 0) pre = ap.prefetch(v);
+      if (act) {
+        for (int i = beg + g; i < end; i += kHotNF * G) {  // kHotNF rows in flight per lane (the tail predicated)
+          float4 x[kHotNF];
+#pragma unroll
+          for (int u = 0; u < kHotNF; ++u) {
+            const int r = i + u * G;
+            x[u] = r < end ? ((const float4*)(pc1 + (size_t)r * sl))[v] : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+#pragma unroll
+          for (int u = 0; u < kHotNF; ++u) add4(acc, x[u]);
+        }
+        red[tid] = acc;
+      }
+      __syncthreads();
+      if (act && g == 0) {
+        for (int q = 1; q < G; ++q) add4(acc, red[q * C + (v - c0)]);
+        ap(v, acc, pre);
+      }
+      __syncthreads();
+    }
+  }
+}
+
 #include "ttx_tt_spec.inc"
 
 static bool spec_shape(const Dims& d) { return spec_match(d) != SPEC_NONE; }
@@ -2040,6 +2331,20 @@ static size_t rows_bytes(const Dims& d, long long nnz) { return align_up((size_t
 
 static TTX_KNOB(int, g_skip_launch, 0);  // ablation (ttx_debug_skip bits 9..11): results invalid when != 0
 static TTX_KNOB(int, g_no_pack, 0);      // A/B (ttx_debug_skip bit 16): reduce_apply with a work-group per small slice, as before round 6
+static TTX_KNOB(int, g_no_small, 0);     // A/B (ttx_debug_skip bit 21): reduce_apply_kernel for the launches reduce_apply_small_kernel would take
+#ifdef TTX_TEST_HOOKS  // (ttx_debug_reduce_route: declared in include/ttx_test_hooks.h, defined beside the knobs' setters below)
+#define TTX_REDUCE_ROUTE(id) (ttx_debug_reduce_route = (id))
+#else
+#define TTX_REDUCE_ROUTE(id) ((void)0)
+#endif
+
+// reduce_apply_small_kernel takes the launch: three cores of whole float4 slices, thin ones of at most 32 lanes, at most
+// kSmallMaxRows lookups (64 segments of the thin cores' hot-slice path: the benchmark batch is 40), no cache rows' scatter riding
+static bool small_route(const Dims& d, long long nnz, const CacheTail* tail) {
+  if ((g_no_small | g_skip_launch) != 0 || d.T != 3 || nnz > kSmallMaxRows || (tail && tail->dst)) return false;
+  if ((d.slice[0] | d.slice[1] | d.slice[2]) & 3) return false;
+  return d.slice[0] <= 4 * 32 && d.slice[2] <= 4 * 32;
+}
 
 // the family's translation unit takes it (ttx_tt_spec{16,32,64,128a,128b,128c}.hip)
 static int run_rows_spec(TTX_SPEC_FWD_ARGS) {
@@ -2126,6 +2431,7 @@ using namespace ttx;
 extern "C" {
 
 #ifdef TTX_TEST_HOOKS  // ---- the knobs' setters: libttx_hooks.so only (include/ttx_test_hooks.h) ----
+int ttx_debug_reduce_route = 0;  // the kernel the last reduce + apply launch was (TTX_REDUCE_FULL / TTX_REDUCE_SMALL; tt_backward_impl writes it)
 // debug: device buffer of 16 int64 stamps per work-group (NULL = off), scripts/phase_times.py
 int ttx_debug_stamps(void* device_buffer) {
   g_stamps = (long long*)device_buffer;
@@ -2139,6 +2445,7 @@ int ttx_debug_skip(int32_t mask) {
   g_no_pack = (mask >> 16) & 1;           // bit 16: no wave-per-slice packing in reduce_apply (results stay valid)
   g_chunk_cols = (mask >> 17) & 1 ? 1 : kChunkCols;  // bit 17: the pivot's chunk list in slot order, not dealt over 8 columns (plans built from here on; results stay valid)
   g_old_stores = (mask >> 18) & 1;        // bit 18: the shape-specialised backward stores its partial gradients as before -- C/D layout, 4-byte non-temporal (results stay valid)
+  g_no_small = (mask >> 21) & 1;          // bit 21: reduce_apply_kernel for the small launches too (results stay valid up to the order of addition)
   g_partial_flavour = (mask >> 19) & 3;   // bits 19..20: flavour of the 16-byte partial stores forced for every launch: 1 non-temporal, 2 write-through, 3 plain (results stay valid)
   g_skip_launch = (mask >> 9) & 63;       // bits 9..11: leave out the pooling launch / reduce_apply / reduce_apply's pivot slices (upper bounds); bit 12: no fused pooling (A/B)
   mask &= 255;
@@ -2183,7 +2490,7 @@ int ttx_debug_tiles(const ttx_geom* g, int32_t* out) {
 // there, and bench.py refuses to time a library where it is not.  In libttx_hooks.so the knobs are plain globals -- not per
 // stream, not thread-safe: tests and A/B timing only.
 int ttx_debug_state(void) {
-  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack | g_old_stores | g_partial_flavour | (g_chunk_cols != kChunkCols)) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
+  return ((g_debug_skip | g_skip_launch | g_disable_spec | g_disable_pad | g_no_pack | g_no_small | g_old_stores | g_partial_flavour | (g_chunk_cols != kChunkCols)) ? 1 : 0) | (g_lds_budget != 160 * 1024 ? 2 : 0) |
          (g_chunk_override ? 4 : 0) | (g_stamps ? 8 : 0) | (ttx_cache_debug_state() << 4);
 }
 
@@ -2656,7 +2963,29 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
     TTX_HIP(hipGetLastError());
     return TTX_OK;
   }
+  if (small_route(d, nnz, tail)) {  // a small launch: reduce_apply_small_kernel (the same hot-slice partition and scratch buffers)
+    SmallRA A;
+    A.w0 = C.c[0]; A.w1 = C.c[1]; A.w2 = C.c[2];
+    A.s0 = S.c[0]; A.s1 = S.c[1]; A.s2 = S.c[2];
+    A.g0 = DW.c[0]; A.g1 = DW.c[1]; A.g2 = DW.c[2];
+    A.seg0 = PC.seg[0]; A.seg2 = PC.seg[2]; A.hot_cnt = PC.hot_cnt;
+    A.S0 = d.S[0]; A.S1 = d.S[1]; A.S2 = d.S[2];
+    A.V0 = d.slice[0] / 4; A.V1 = d.slice[1] / 4; A.V2 = d.slice[2] / 4;
+    A.nthin = (d.S[0] + d.S[2] + kSmallSlices - 1) / kSmallSlices;
+    A.hp = (A.V1 + kSmallPivotCols - 1) / kSmallPivotCols;
+    A.npiv = d.S[1] * A.hp;
+    A.nseg = num_segments(d, nnz, MC, 0);  // (= core 2's: a segment per kSegThin lookups of the sorted order)
+    A.optim = optim; A.lr = lr; A.eps = eps;
+    const int ncol = hot_wgs(P.max_chunks, d.slice[1], 1);
+    ProfScope ps(TTX_PROF_APPLY, st);
+    hipLaunchKernelGGL(reduce_apply_small_kernel, dim3(A.nthin + A.npiv + 2 * A.nseg + ncol), dim3(kSmallThreads), 0, st, P.off[0],
+                       P.chunk_off, P.off[2], P.hdr, PC.pc[0], PC.pc[1], PC.pc[2], A);
+    TTX_HIP(hipGetLastError());
+    TTX_REDUCE_ROUTE(TTX_REDUCE_SMALL);
+    return TTX_OK;
+  }
   if (!(g_skip_launch & 2)) {
+    TTX_REDUCE_ROUTE(TTX_REDUCE_FULL);
     int smax = 0;
     for (int t = 0; t < d.T; ++t) smax = d.slice[t] > smax ? d.slice[t] : smax;
     int rthreads = smax <= 4096 ? TTX_RTHREADS_SMALL : kReduceThreads;  // (measured: 512 is 1.7 us faster at r = 32, 1024 at r = 64)

@@ -1382,7 +1382,8 @@ def debug_skip(mask: int) -> None:
     """bit 8: force the generic kernels; bit 15: exact-shape templates only; bit 16: reduce_apply with a work-group (not a wave) per
     small slice; bit 17: plans list the pivot's chunks in slot order (one column) instead of dealing them over 8 columns, one per
     XCD; bit 18: the shape-specialised backward stores its partial gradients as 4-byte non-temporal stores, as before the 16-byte
-    ones; bits 19..20: the flavour of the 16-byte partial stores forced for every launch (1 non-temporal, 2 write-through, 3 plain)
+    ones; bits 19..20: the flavour of the 16-byte partial stores forced for every launch (1 non-temporal, 2 write-through, 3 plain);
+    bit 21: reduce_apply_kernel also for the small launches reduce_apply_small_kernel takes
     -- these leave the results valid; the other bits skip kernel phases / launches (results INVALID).  0 = normal operation."""
     _check(hooks_lib().ttx_debug_skip(int(mask)))
     _knobs_changed()
@@ -1439,6 +1440,15 @@ def debug_plan_route() -> int:
         hooks_lib()
         _knobs_changed()
     return int(_hooks.ttx_debug_plan_route())
+
+
+def debug_reduce_route() -> int:
+    """Test helper (ttx_debug_reduce_route, a global of the TEST library): the kernel its last reduce + apply launch was --
+    0 none yet, 1 reduce_apply_kernel, 2 reduce_apply_small_kernel.  Run the backward inside `with test_library():`."""
+    if _hooks is None:
+        hooks_lib()
+        _knobs_changed()
+    return int(C.c_int.in_dll(_hooks, "ttx_debug_reduce_route").value)
 
 
 def debug_tiles(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> dict:

@@ -27,8 +27,14 @@ int ttx_debug_lds_budget(int32_t bytes);
  * performance only: results stay bit-identical); bit 18 the shape-specialised backward stores its partial gradients as 4-byte
  * non-temporal stores from products in the C/D layout, as before the 16-byte stores (results stay bit-identical);
  * bits 19..20 force the flavour of the 16-byte partial stores for every launch: 1 non-temporal, 2 write-through, 3 plain (timing
- * only: results stay bit-identical).  0 = normal operation. */
+ * only: results stay bit-identical); bit 21 reduce_apply_kernel also for the small launches that reduce_apply_small_kernel takes
+ * (results stay valid up to the order of addition).  0 = normal operation. */
 int ttx_debug_skip(int32_t mask);
+/* The kernel the LAST reduce + apply launch of this process was (a plain global of the test library, written by the backward's
+ * host code): 0 = none yet, TTX_REDUCE_FULL = reduce_apply_kernel, TTX_REDUCE_SMALL = reduce_apply_small_kernel. */
+#define TTX_REDUCE_FULL 1
+#define TTX_REDUCE_SMALL 2
+extern int ttx_debug_reduce_route;
 /* A/B knob (scripts/bench_cache.py): 1 = ttx_cache_forward uses the one-group-per-lookup kernel for every D */
 int ttx_debug_cache_fwd(int32_t lookup_groups);
 /* (scripts/phase_times.py) device buffer receiving 16 int64 wall-clock stamps per backward work-group; NULL = off */
