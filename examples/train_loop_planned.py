@@ -8,7 +8,8 @@
      become gathers from then on,
   3. steady state, a round of queued batches at a time: `prefetch_many(batches)` plans the round's lookups ahead
      (frequency update, cache lookup, hit / miss partition and the miss plans of all batches in three launches:
-     index work that depends on the batches only, not on the weights), then the steps follow without it,
+     index work that depends on the batches only, not on the weights), then the steps follow without it; between rounds
+     `cache_populate(keep_trained=True, freq_shift=1)` refreshes the cache without dropping what its rows learnt,
   4. the same round captured in a hipGraph and replayed (ttx_graph.GraphedRound): one graph launch per round.
 
 Nothing here differs in RESULT from calling `emb(indices, offsets)` step by step; only where the index work runs."""
@@ -56,7 +57,12 @@ def main():
     emb.cache_populate()
     # 3. steady state, a round of 8 queued batches at a time
     queue = [(i.to(dev), o.to(dev)) for i, o in zipf_batches(8, B, L, E, seed=2)]
-    for _ in range(3):
+    for rnd_no in range(3):
+        if rnd_no > 0:
+            # refresh the semi-dynamic cache every round (in practice: every few thousand steps).  The live steps kept counting;
+            # keep_trained: keys that stay cached keep their trained rows and optimizer state, new keys are decompressed from the
+            # cores; freq_shift=1 halves the counts first, so that an old hot key leaves once it has gone cold
+            emb.cache_populate(keep_trained=True, freq_shift=1)
         planned = emb.prefetch_many(queue)  # False where the module cannot plan ahead (then every step plans itself)
         for i, o in queue:
             loss = step(i, o)

@@ -15,18 +15,6 @@ namespace ttx {
 
 constexpr int kCT = 256;
 
-// hashtbl_cuda_utils.cuh:135-154 (incl. the early-out on the SEARCH key, :146)
-__device__ __forceinline__ int32_t hashtbl_find(int64_t key, int32_t size, const int64_t* keys) {
-  int32_t idx = (int32_t)hash64(key, size);
-#pragma unroll
-  for (int c = 0; c < kMaxProbes; ++c) {
-    if (key == keys[idx]) return idx;
-    else if (key == -1) return -1;
-    idx = (idx + 1) % size;
-  }
-  return -1;
-}
-
 // hashtbl_cuda_utils.cuh:102-133 with accumulate == true: 64-bit CAS claims the
 // slot, 64-bit atomic add bumps the frequency.
 __global__ __launch_bounds__(kCT) void update_cache_state_kernel(

@@ -306,10 +306,22 @@ __device__ __forceinline__ uint32_t hash64(int64_t key, int32_t C) {
   return (uint32_t)(((uint64_t)h * (uint64_t)(uint32_t)C) >> 32);
 }
 
+// hashtbl_cuda_utils.cuh:135-154 (incl. the early-out on the SEARCH key, :146)
+__device__ __forceinline__ int32_t hashtbl_find(int64_t key, int32_t size, const int64_t* keys) {
+  int32_t idx = (int32_t)hash64(key, size);
+#pragma unroll
+  for (int c = 0; c < kMaxProbes; ++c) {
+    if (key == keys[idx]) return idx;
+    else if (key == -1) return -1;
+    idx = (idx + 1) % size;
+  }
+  return -1;
+}
+
 // hashtbl_cuda_utils.cuh:102-133 with accumulate == true: a 64-bit CAS claims the slot (or finds
 // the key already there), a 64-bit atomic add bumps its frequency; dropped after kMaxProbes.
 // -> the slot the key was counted in, -1 if it was dropped.  That slot is the first one of the key's probe sequence that holds
-// the key once this launch's inserts are done -- i.e. what hashtbl_find (ttx_cache.hip) returns AFTER the update, for every copy
+// the key once this launch's inserts are done -- i.e. what hashtbl_find (above) returns AFTER the update, for every copy
 // of the key in the launch alike (a slot seen holding another key keeps it; an empty one goes to whoever's CAS lands, and every
 // later CAS on it returns that winner).
 __device__ __forceinline__ int32_t hashtbl_count(int64_t key, int32_t H, int64_t* hashtbl, int64_t* cache_freq,

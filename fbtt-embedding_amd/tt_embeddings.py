@@ -18,7 +18,7 @@ the batch share one contraction),
 `bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, the unpooled lookup's `rows_expand` /
 `rows_collect` (and, with a live cache, `preprocess_indices_async`, `rows_place` / `rows_pick`), `bags_merge` (the per-table
 batches of a mixed-cardinality group -> one table-major batch, one launch), and the row cache over several tables' `table_keys`,
-`table_keys_split` and `cache_populate_tables`.
+`table_keys_split` and `cache_populate_tables`, and `cache_carry` (trained cache rows and their state across a re-populate).
 """
 import ctypes as C
 import os
@@ -196,6 +196,8 @@ def _load(path):
     L.ttx_cache_populate_v_workspace_bytes.restype = C.c_size_t
     L.ttx_cache_populate_v_workspace_bytes.argtypes = [G, i64, i64, i32]
     L.ttx_cache_populate_v.argtypes = [G, vp, i64, vp, vp, vp, i64, i32, vp, i32, vp, sz, vp]
+    # cache refresh: trained rows and their optimizer state across a re-populate
+    L.ttx_cache_carry.argtypes = [i64, vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     return L
@@ -767,6 +769,46 @@ def cache_populate_var_tables(tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores, hash
         _check(lb.ttx_cache_populate_v(C.byref(g), _ptr_array(cores), H, hashtbl.data_ptr(), cache_freq.data_ptr(),
                                        cache_state.data_ptr(), cs, D, cw.data_ptr(), 1 if reference_exact else 0,
                                        ws.data_ptr(), ws.numel(), st))
+
+
+def cache_carry(hashtbl: torch.Tensor, old_state: torch.Tensor, cache_state: torch.Tensor, old_weight: torch.Tensor,
+                cache_weight: torch.Tensor, old_opt_state: Optional[torch.Tensor] = None,
+                opt_state: Optional[torch.Tensor] = None) -> None:
+    """Not in the reference: after a populate (any of the three above), move what the cache had learnt to where it now belongs
+    (ttx_cache_carry).  `old_state` / `old_weight` / `old_opt_state` are copies of cache_state / cache_weight / the cache rows'
+    optimizer state taken BEFORE the populate.  A key cached before and after gets its old row and state in its new row; a key
+    new to the cache keeps the decompressed row and zero state; rows no key owns are not written.  The state is [cache_size]
+    (row-wise) or [cache_size, D] (element-wise), both or neither given."""
+    dev = _dev(cache_weight)
+    _i64(hashtbl, "hashtbl")
+    H = hashtbl.numel()
+    cw, ow = cache_weight.detach(), old_weight.detach()
+    for name, t in (("cache_weight", cw), ("old_weight", ow)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise RuntimeError(f"tt_embeddings: {name} must be contiguous float32 [cache_size, D]")
+    if ow.shape != cw.shape:
+        raise RuntimeError("tt_embeddings: old_weight must have cache_weight's shape")
+    cs, D = cw.size(0), cw.size(1)
+    if H <= 0 or H < cs or not hashtbl.is_contiguous():
+        raise RuntimeError("tt_embeddings: need a contiguous hashtbl with 0 < hashtbl.numel() >= cache_size")
+    for name, t in (("cache_state", cache_state), ("old_state", old_state)):
+        if t.dtype != torch.int32 or t.numel() != H or not t.is_contiguous():
+            raise RuntimeError(f"tt_embeddings: {name} must be contiguous int32[hashtbl_size]")
+    width, sp, osp = 0, None, None
+    if (opt_state is None) != (old_opt_state is None):
+        raise RuntimeError("tt_embeddings: opt_state and old_opt_state go together")
+    if opt_state is not None:
+        for name, t in (("opt_state", opt_state), ("old_opt_state", old_opt_state)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) not in ((cs,), (cs, D)):
+                raise RuntimeError(f"tt_embeddings: {name} must be contiguous float32 [cache_size] or [cache_size, D]")
+        if old_opt_state.shape != opt_state.shape:
+            raise RuntimeError("tt_embeddings: old_opt_state must have opt_state's shape")
+        width, sp, osp = (1 if opt_state.dim() == 1 else D), opt_state.data_ptr(), old_opt_state.data_ptr()
+    if any(t.device != dev for t in (hashtbl, old_state, cache_state, ow) + (() if opt_state is None else (opt_state, old_opt_state))):
+        raise RuntimeError(f"tt_embeddings: every cache_carry tensor must be on {dev}")
+    with _guard(dev):
+        _check(lib().ttx_cache_carry(H, hashtbl.data_ptr(), old_state.data_ptr(), cache_state.data_ptr(), cs, D, ow.data_ptr(),
+                                     cw.data_ptr(), width, osp, sp, _stream(dev)))
 
 
 def preprocess_indices_sync(colidx: torch.Tensor, offsets: torch.Tensor, num_tables: int, warmup: bool,

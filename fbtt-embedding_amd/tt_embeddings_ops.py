@@ -998,14 +998,63 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             first = table * space
         _engine.update_cache_state((indices + first).contiguous(), self.hashtbl, self.cache_freq)
 
-    def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1) -> None:
+    def _refresh_check(self, keep_trained: bool, freq_shift: int) -> None:
+        """what cache_populate(keep_trained=, freq_shift=) refuses -- before anything is changed"""
+        if isinstance(freq_shift, bool) or not hasattr(freq_shift, "__index__") or not 0 <= int(freq_shift) < 63:
+            raise ValueError(f"cache_populate(freq_shift={freq_shift!r}): an integer in [0, 63)")
+        if keep_trained and self.use_cache:
+            if self.reference_exact_populate:
+                raise ValueError("cache_populate(keep_trained=True) reads the cache_state of every slot, and with "
+                                 "reference_exact_populate=True evicted slots keep stale ones: use one or the other")
+            if getattr(_engine, "cache_carry", None) is None or not self.cache_weight.is_cuda:
+                raise NotImplementedError("cache_populate(keep_trained=True) moves the rows on the GPU only")
+
+    def _refresh_begin(self, keep_trained: bool, freq_shift: int):
+        """in front of the populate's sort: age the frequencies (cache_freq >>= freq_shift) and, for keep_trained on a live
+        cache, copy what the populate overwrites -> (cache_state, cache_weight, state or None) as they were, or None"""
+        if not self.use_cache:
+            return None
+        if int(freq_shift) > 0:
+            self.cache_freq.bitwise_right_shift_(int(freq_shift))
+        if not keep_trained or self.warmup:  # (still warming up: no row has been trained)
+            return None
+        state = self._cache_row_state()
+        return self.cache_state.clone(), self.cache_weight.detach().clone(), None if state is None else state.clone()
+
+    def _cache_row_state(self) -> Optional[torch.Tensor]:
+        """the cache rows' optimizer state as the update kernels use it: ONE float per row, the first cache_size floats of the
+        buffer whatever its shape ([cache_size, D] under EXACT_ADAGRAD, as in the reference -- the cache rows' update is the
+        row-wise one for both Adagrad kinds); a view"""
+        state = self.cache_optimizer_state
+        return None if state is None else state.view(-1)[:self.cache_weight.size(0)]
+
+    def _refresh_end(self, old) -> None:
+        """behind the populate: kept keys get their trained rows and state back, admitted keys start from zero state"""
+        if old is not None:
+            _engine.cache_carry(self.hashtbl, old[0], self.cache_state, old[1], self.cache_weight, old[2], self._cache_row_state())
+
+    def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1, keep_trained: bool = False,
+                       freq_shift: int = 0) -> None:
         """tt_embeddings_ops.py:800-814.  `write_back` (NOT in the reference; default 0 = its behaviour): cached rows are trained
         directly, and a populate decompresses every cache row anew from the cores -- what the cached copies learnt since the last
         populate is dropped.  A dense row has no exact TT representation, so there is no inverse; with write_back = lr > 0 the
         cores first take `write_back_steps` fused SGD steps of that size toward the cached rows (gradient of 1/2 ||TT row - cached row||^2
         for every cached key, through the ordinary forward / backward contraction), which moves the TT rows toward what the cache
         learnt -- an approximation (the cached keys share core slices: a few steps recover part of the difference, measured in
-        tests/test_module_cpu.py), off by default."""
+        tests/test_module_cpu.py), off by default.
+
+        `keep_trained` (NOT in the reference; default False = its behaviour): a key that is cached before and
+        after the populate keeps its trained row and the row's fused optimizer state, whatever row number it moves to; a key new
+        to the cache gets the freshly decompressed row and zero state.  Exact, GPU only, refused together with
+        reference_exact_populate; costs a transient copy of cache_weight (and state).  While the module still warms up there is
+        nothing to keep.  With write_back the cores move first: kept rows keep their values, admitted rows decompress from the
+        moved cores.  With sparse=False only the weights move -- an external optimizer's per-row state (momentum, Adam moments
+        of cache_weight) is the caller's business.
+
+        `freq_shift` = k in [0, 63) (NOT in the reference; default 0): cache_freq >>= k in front of the sort.  A populate zeroes
+        the count of every key it evicts while cached keys keep counting from the start of the run, so without ageing the
+        incumbents never leave; halving (k = 1) at every refresh makes the counts an exponential average."""
+        self._refresh_check(keep_trained, freq_shift)
         if self._tables_cache():
             if write_back > 0.0:
                 raise NotImplementedError("cache_populate(write_back > 0) is not supported by the row cache over several tables")
@@ -1013,8 +1062,10 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             if populate is None or not self.cache_weight.is_cuda:
                 raise NotImplementedError("the row cache over several tables is populated on the GPU only")
             extra = {"reference_exact": True} if self.reference_exact_populate else {}
+            old = self._refresh_begin(keep_trained, freq_shift)
             populate(self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), self.hashtbl,
                      self.cache_freq, self.cache_state, self.cache_weight, self._key_stride(), **extra)
+            self._refresh_end(old)
             self.warmup = False
             self._drop_prefetched()
             return
@@ -1022,9 +1073,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             self._write_back(write_back, write_back_steps)
         if self.use_cache:
             extra = {"reference_exact": True} if self.reference_exact_populate else {}
+            old = self._refresh_begin(keep_trained, freq_shift)
             _engine.cache_populate(self.num_embeddings, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks,
                                    list(self.tt_cores), self.L, self.hashtbl, self.cache_freq, self.cache_state,
                                    self.cache_weight, **extra)
+            self._refresh_end(old)
             self.warmup = False
             self._drop_prefetched()  # (a planned-ahead batch was split into hits / misses by the OLD cache contents)
 

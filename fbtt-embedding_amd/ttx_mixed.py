@@ -222,9 +222,12 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         factors)"""
         return bool(self.use_cache)
 
-    def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1) -> None:
+    def cache_populate(self, write_back: float = 0.0, write_back_steps: int = 1, keep_trained: bool = False,
+                       freq_shift: int = 0) -> None:
         """the cache_size most frequent keys get the cache rows, each decompressed from its own table (ttx_cache_populate_v); the
-        cache is live from here on.  GPU only; no `write_back`."""
+        cache is live from here on.  GPU only; no `write_back`.  `keep_trained` / `freq_shift`: as the parent's (keys cached
+        before and after keep their trained rows and state; cache_freq >>= freq_shift in front of the sort)."""
+        self._refresh_check(keep_trained, freq_shift)
         if not self.use_cache:
             return
         if write_back > 0.0:
@@ -233,8 +236,10 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         if populate is None or not self.cache_weight.is_cuda:
             raise NotImplementedError("the row cache over tables of different row factors is populated on the GPU only")
         extra = {"reference_exact": True} if self.reference_exact_populate else {}
+        old = self._refresh_begin(keep_trained, freq_shift)
         populate(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), self.hashtbl, self.cache_freq,
                  self.cache_state, self.cache_weight, **extra)
+        self._refresh_end(old)
         self.warmup = False
         self._drop_prefetched()
 
@@ -484,10 +489,12 @@ class MixedTTEmbeddingBag(nn.Module):
             if streams and len(self.groups) > 1 else None
 
     # ------------------------------------------------------------------ the groups' row caches (use_cache=True)
-    def cache_populate(self) -> None:
-        """every group's cache_populate(): the groups' caches are live from here on"""
+    def cache_populate(self, keep_trained: bool = False, freq_shift: int = 0) -> None:
+        """every group's cache_populate(keep_trained=, freq_shift=): the groups' caches are live from here on"""
+        for mod in self.groups:  # (refusals first: no group is populated when one of them refuses)
+            mod._refresh_check(keep_trained, freq_shift)
         for mod in self.groups:
-            mod.cache_populate()
+            mod.cache_populate(keep_trained=keep_trained, freq_shift=freq_shift)
 
     def reset_cache(self) -> None:
         for mod in self.groups:

@@ -703,6 +703,33 @@ int ttx_cache_populate_v(const ttx_geom* g, const float* const* tt_cores, int64_
                          int64_t* cache_freq, int32_t* cache_state, int64_t cache_size, int32_t D, float* cache_weight,
                          int32_t flags, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
 
+/* ------------------------------ cache refresh: trained rows across a re-populate (not in the reference) -----
+ * Every populate above decompresses all cache_size rows anew, so what the cached rows learnt since the last populate is lost,
+ * and the rows' optimizer state stays where it was while the keys change rows.  ttx_cache_carry runs AFTER any of the populates
+ * (with flags = 0) and puts both where they belong, given copies of cache_state / cache_weight / the state taken BEFORE it.
+ *
+ *   per hash slot s in [0, hashtbl_size):  k = hashtbl[s], n = cache_state[s], m = old_state[s].  The slot takes part iff
+ *       k != -1,  0 <= n < cache_size,  and  s is the slot the library's own probe finds k in (3 probes).
+ *     (The last condition: a key can sit in two slots of its probe window -- an eviction emptied an earlier slot, a later count
+ *      re-inserted the key there -- and the later copy then carries a stale cache_state that may name a row another key owns
+ *      by now.  Only the findable copy owns its row.)
+ *   kept      (0 <= m < cache_size):  cache_weight[n, :] = old_weight[m, :],  opt_state[n, :] = old_opt_state[m, :]
+ *   admitted  (otherwise):            cache_weight[n, :] stays what the populate decompressed,  opt_state[n, :] = 0
+ *   Rows that no participating slot owns are not written.
+ *
+ * state_width: 0 = no optimizer state (both state pointers are ignored), 1 = one float per row (row-wise Adagrad),
+ * D = one per element; the state arrays are [cache_size, state_width].  One writer per row by construction: no atomics, no
+ * read-back (capturable), bit-deterministic.  One launch: the slots are scanned with coalesced reads, a row is moved by a group
+ * of lanes with 16-byte accesses when D % 4 == 0 and the row arrays are 16-byte aligned, float by float otherwise.
+ *   cache_size == 0   returns 0 and launches nothing.
+ *   errors            hashtbl_size outside (0, 2^31), cache_size < 0 or > hashtbl_size, D <= 0, state_width not in {0, 1, D},
+ *                     hashtbl not 8-byte (any other pointer: 4-byte) aligned, a NULL pointer that would be read or written,
+ *                     old_weight overlapping cache_weight or old_opt_state overlapping opt_state (the move is a permutation:
+ *                     it cannot be done in place): -1 with ttx_last_error() set, before anything touches a device. */
+int ttx_cache_carry(int64_t hashtbl_size, const int64_t* hashtbl, const int32_t* old_state, const int32_t* cache_state,
+                    int64_t cache_size, int32_t D, const float* old_weight, float* cache_weight, int32_t state_width,
+                    const float* old_opt_state, float* opt_state, ttx_stream_t stream);
+
 /* replaces cache_forward_cuda (tt_embeddings.cpp:97-103,
  * tt_embeddings_cuda.cu:1498-1572): output[rowidx[n], :] += cache_weight[
  * cache_locations[n], :], summed per run of equal rowidx. */
