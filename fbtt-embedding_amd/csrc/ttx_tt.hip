@@ -2249,14 +2249,22 @@ __global__ __launch_bounds__(kT4Threads) void t4_apply23_kernel(Plan P, const fl
     const int g = tid / V, v = tid - g * V;
     float acc = 0.f;
     if (g < G) {
+      // a sum per row in flight, folded at the end: a slice of 87,381 rows (262,144 lookups over five slices) summed into ONE
+      // accumulator per thread -- 43,690 additions in a row at G = 2 -- ended 5.7 default bounds from float64 (the fp32 oracle's own
+      // left-to-right sum: 4.9); eight chains of an eighth of the length and an eighth of the magnitude: 0.41
+      // (tests/test_t4_routes_gpu.py, profiles/t4_routes_tolerances.md).  Fewer than 8 G rows: the sum is what it was, bit for bit.
+      float a8[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) a8[u] = 0.f;
       int r = beg + g;
       for (; r + 7 * G < end; r += 8 * G) {
         float x[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) x[u] = pc[(size_t)(r + u * G) * sl + e0 + v];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc += x[u];
+        for (int u = 0; u < 8; ++u) a8[u] += x[u];
       }
+      acc = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
       for (; r < end; r += G) acc += pc[(size_t)r * sl + e0 + v];
     }
     __syncthreads();
@@ -2268,6 +2276,11 @@ __global__ __launch_bounds__(kT4Threads) void t4_apply23_kernel(Plan P, const fl
     }
   }
 }
+#ifdef TTX_TEST_HOOKS  // (ttx_debug_t4_route: what this route's host code chose, for the tests -- include/ttx_test_hooks.h; defined beside the knobs' setters)
+#define TTX_T4_ROUTE(k, v) (ttx_debug_t4_route[k] = (int)(v))
+#else
+#define TTX_T4_ROUTE(k, v) ((void)0)
+#endif
 static int t4_grid(long long work) {
   const long long b = (work + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
@@ -2294,12 +2307,14 @@ static int t4_merge(const Dims& d, long long nnz, const Plan& P, const float* c2
     // the reuse (10k lookups, ms/step: 4 -> 0.221, 8 -> 0.225, 16 -> 0.244, 32 -> 0.273; the per-lookup form 0.247)
     const int seg = nnz >= (1 << 17) ? 32 : (nnz >= (1 << 15) ? 16 : 4);
     const size_t lds = (size_t)seg * d.r[3] * d.q[3] * sizeof(float);
+    TTX_T4_ROUTE(TTX_T4_MERGE_FORM, TTX_T4_MERGE_SORTED); TTX_T4_ROUTE(TTX_T4_MERGE_SEG, seg); TTX_T4_ROUTE(TTX_T4_MERGE_GRID, (nnz + seg - 1) / seg);
 #define TTX_T4_CALL(Q) hipLaunchKernelGGL(t4_merge_sorted_kernel<Q>, dim3((unsigned)((nnz + seg - 1) / seg)), dim3(threads), lds, st, P, c2, c3, P.t4m, r2q2, d.r[3], seg, reuse)
     TTX_T4_Q3(d.q[3], TTX_T4_CALL)
 #undef TTX_T4_CALL
     TTX_HIP(hipGetLastError());
     return TTX_OK;
   }
+  TTX_T4_ROUTE(TTX_T4_MERGE_FORM, TTX_T4_MERGE_PER_LOOKUP); TTX_T4_ROUTE(TTX_T4_MERGE_SEG, 0); TTX_T4_ROUTE(TTX_T4_MERGE_GRID, t4_grid(nnz * r2q2));
 #define TTX_T4_CALL(Q) hipLaunchKernelGGL(t4_merge_kernel<Q>, dim3(t4_grid(nnz * r2q2)), dim3(256), 0, st, P, c2, c3, P.t4m, r2q2, d.r[3])
   TTX_T4_Q3(d.q[3], TTX_T4_CALL)
 #undef TTX_T4_CALL
@@ -2431,6 +2446,7 @@ using namespace ttx;
 extern "C" {
 
 #ifdef TTX_TEST_HOOKS  // ---- the knobs' setters: libttx_hooks.so only (include/ttx_test_hooks.h) ----
+int ttx_debug_t4_route[TTX_T4_ROUTE_INTS] = {0};  // what the four-core route's host code chose last (TTX_T4_ROUTE)
 int ttx_debug_reduce_route = 0;  // the kernel the last reduce + apply launch was (TTX_REDUCE_FULL / TTX_REDUCE_SMALL; tt_backward_impl writes it)
 // debug: device buffer of 16 int64 stamps per work-group (NULL = off), scripts/phase_times.py
 int ttx_debug_stamps(void* device_buffer) {
@@ -2879,8 +2895,11 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
     const bool t4_mfma = !t4_valu && r2q2 % 16 == 0 && d.r[3] % 16 == 0 && n2 / 256 <= 32;
     const T4Lds TL = t4_lds(r2q2, d.r[3], d.q[3]);
     const size_t lds_m = (size_t)TL.floats * sizeof(float);
+    TTX_T4_ROUTE(TTX_T4_SEG, SEG); TTX_T4_ROUTE(TTX_T4_HELPER_Q3, d.q[3]); TTX_T4_ROUTE(TTX_T4_APPLY_SEG, 0);
+    TTX_T4_ROUTE(TTX_T4_LDS_BYTES, t4_mfma ? lds_m : lds); TTX_T4_ROUTE(TTX_T4_LDS_OPT_IN, (t4_mfma ? lds_m : lds) > 64 * 1024);
 #define TTX_T4_MFMA(Q)                                                                                                          \
     do {                                                                                                                         \
+      TTX_T4_ROUTE(TTX_T4_HELPER, n2 / 256 <= 16 ? TTX_T4_HELPER_MFMA4 : TTX_T4_HELPER_MFMA8);                                   \
       if (n2 / 256 <= 16) {                                                                                                       \
         if (lds_m > 64 * 1024) { rc = allow_lds(t4_grad23_mfma_kernel<Q, 4>, (int)lds_m); if (rc) return rc; }                    \
         hipLaunchKernelGGL((t4_grad23_mfma_kernel<Q, 4>), dim3(gblocks), dim3(kT4Threads), lds_m, st, P, tt_cores[2], tt_cores[3],\
@@ -2899,6 +2918,7 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
                                   : (n2 <= 16 * kT4Threads ? allow_lds(t4_grad23_kernel<Q, 16>, (int)lds) : allow_lds(t4_grad23_kernel<Q, 32>, (int)lds)); \
         if (rc) return rc;                                                                                                        \
       }                                                                                                                          \
+      TTX_T4_ROUTE(TTX_T4_HELPER, n2 <= 8 * kT4Threads ? TTX_T4_HELPER_VALU8 : (n2 <= 16 * kT4Threads ? TTX_T4_HELPER_VALU16 : TTX_T4_HELPER_VALU32)); \
       if (n2 <= 8 * kT4Threads)                                                                                                   \
         hipLaunchKernelGGL((t4_grad23_kernel<Q, 8>), dim3(gblocks), dim3(kT4Threads), lds, st, P, tt_cores[2], tt_cores[3], P.t4g, \
                            PC.pc[2], PC.pc[3], r2q2, d.r[3], SEG);                                                               \
@@ -2955,6 +2975,7 @@ static int tt_backward_impl(const ttx_geom* g, int32_t optim, int32_t B, int32_t
     const int smax = d.slice[0] > d.slice[1] ? d.slice[0] : d.slice[1];
     const int rthreads = smax <= 4096 ? TTX_RTHREADS_SMALL : kReduceThreads;
     ProfScope ps(TTX_PROF_APPLY, st);
+    TTX_T4_ROUTE(TTX_T4_APPLY_SEG, t4_seg(nnz));
     hipLaunchKernelGGL(reduce_apply_kernel, dim3(ns2 + nsg2), dim3(rthreads), reduce_lds_bytes(rthreads), st, d2, P, PC, optim, lr, eps, C, S, DW, ns2,
                        (int)nnz, CacheTail{}, 1);
     TTX_HIP(hipGetLastError());

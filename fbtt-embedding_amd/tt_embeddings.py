@@ -1493,6 +1493,23 @@ def debug_reduce_route() -> int:
     return int(C.c_int.in_dll(_hooks, "ttx_debug_reduce_route").value)
 
 
+T4_ROUTE_FIELDS = ("merge_form", "merge_seg", "merge_grid", "seg", "helper", "lds_bytes", "lds_opt_in", "apply_seg", "q3")
+
+
+def debug_t4_route(clear: bool = False) -> dict:
+    """Test helper (ttx_debug_t4_route, a global of the TEST library): what the host code of the four-core route chose for its
+    last launch (include/ttx_test_hooks.h TTX_T4_*; zeros: none yet).  Run the launch inside `with test_library():`.
+    clear: zero the record after reading it, so that the next read shows the next launch alone."""
+    if _hooks is None:
+        hooks_lib()
+        _knobs_changed()
+    rec = (C.c_int * len(T4_ROUTE_FIELDS)).in_dll(_hooks, "ttx_debug_t4_route")
+    out = dict(zip(T4_ROUTE_FIELDS, (int(x) for x in rec)))
+    if clear:
+        rec[:] = [0] * len(T4_ROUTE_FIELDS)
+    return out
+
+
 def debug_tiles(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> dict:
     """Test helper: the block walk the generic kernels take for this geometry under the current budget."""
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)

@@ -35,6 +35,28 @@ int ttx_debug_skip(int32_t mask);
 #define TTX_REDUCE_FULL 1
 #define TTX_REDUCE_SMALL 2
 extern int ttx_debug_reduce_route;
+/* What the host code of the four-core route (csrc/ttx_tt.hip: t4_merge, the helper dispatch of the backward, the launch of
+ * t4_apply23_kernel) chose for the LAST launch of this process that took it (a plain global of the test library; zeros: none yet;
+ * tests/t4_ref.py is the host mirror the tests compare it with).  The merge fields are written by the forward AND the backward
+ * (both launch the merge), the others by the backward. */
+#define TTX_T4_MERGE_FORM 0   /* TTX_T4_MERGE_SORTED = t4_merge_sorted_kernel, TTX_T4_MERGE_PER_LOOKUP = t4_merge_kernel */
+#define TTX_T4_MERGE_SEG 1    /* positions per work-group of the sorted form; 0 for the per-lookup form */
+#define TTX_T4_MERGE_GRID 2   /* work-groups of the merge launch */
+#define TTX_T4_SEG 3          /* SEG the gradient helper was launched with */
+#define TTX_T4_HELPER 4       /* TTX_T4_HELPER_* */
+#define TTX_T4_LDS_BYTES 5    /* its dynamic LDS */
+#define TTX_T4_LDS_OPT_IN 6   /* 1 = more than 64 KiB: the launch went through allow_lds */
+#define TTX_T4_APPLY_SEG 7    /* SEG t4_apply23_kernel was launched with; 0 = the launch was left out */
+#define TTX_T4_HELPER_Q3 8    /* the helpers' template argument Q3 */
+#define TTX_T4_ROUTE_INTS 9
+#define TTX_T4_MERGE_SORTED 1
+#define TTX_T4_MERGE_PER_LOOKUP 2
+#define TTX_T4_HELPER_MFMA4 1 /* t4_grad23_mfma_kernel<Q3, 4> */
+#define TTX_T4_HELPER_MFMA8 2 /* t4_grad23_mfma_kernel<Q3, 8> */
+#define TTX_T4_HELPER_VALU8 3 /* t4_grad23_kernel<Q3, 8> */
+#define TTX_T4_HELPER_VALU16 4
+#define TTX_T4_HELPER_VALU32 5
+extern int ttx_debug_t4_route[TTX_T4_ROUTE_INTS];
 /* A/B knob (scripts/bench_cache.py): 1 = ttx_cache_forward uses the one-group-per-lookup kernel for every D */
 int ttx_debug_cache_fwd(int32_t lookup_groups);
 /* (scripts/phase_times.py) device buffer receiving 16 int64 wall-clock stamps per backward work-group; NULL = off */

@@ -82,7 +82,8 @@ def test_product_library_has_no_test_knobs():
     ttx_debug_cache_fwd) and the process-wide reference-exact switch are NOT in libttx.so -- neither the setters nor a global to
     set -- and the library exports its C ABI only.  They live in libttx_hooks.so, the same sources with -DTTX_TEST_HOOKS
     (include/ttx_test_hooks.h), which the shim loads on the first use of a knob and leaves as soon as every knob is back at
-    its default."""
+    its default.  The same holds for the globals the test library's host code writes for the tests to read
+    (ttx_debug_reduce_route, ttx_debug_t4_route)."""
     import subprocess
 
     import tt_embeddings as E
@@ -91,15 +92,19 @@ def test_product_library_has_no_test_knobs():
     knobs = sorted(set(re.findall(r"\b(ttx_[a-z0-9_]+)\s*\(", hooks_hdr)))
     assert set(knobs) == {"ttx_set_chunk", "ttx_debug_lds_budget", "ttx_debug_skip", "ttx_debug_cache_fwd", "ttx_debug_stamps",
                           "ttx_debug_plan_layout", "ttx_debug_plan_route"}  # (the last two change nothing: how the plan tests see a plan)
+    # ... and the globals the host code writes for the tests to read (what ran: neither changes what the library does)
+    records = sorted(set(re.findall(r"\bextern\s+int\s+(ttx_[a-z0-9_]+)", hooks_hdr)))
+    assert records == ["ttx_debug_reduce_route", "ttx_debug_t4_route"]
     so = os.path.join(ROOT, "fbtt-embedding_amd", "libttx.so")
     exported = [ln.split()[-1] for ln in subprocess.check_output(["nm", "-D", "--defined-only", so], text=True).splitlines()]
     assert exported and all(sym.startswith("ttx_") for sym in exported), [x for x in exported if not x.startswith("ttx_")]
-    for sym in knobs + ["ttx_set_reference_exact"]:
+    for sym in knobs + records + ["ttx_set_reference_exact"]:
         assert sym not in exported, f"{sym} is exported by the product library"
     prod = ctypes.CDLL(so)
     assert prod.ttx_has_test_hooks() == 0 and prod.ttx_debug_state() == 0
     hooks = ctypes.CDLL(os.path.join(ROOT, "fbtt-embedding_amd", "libttx_hooks.so"))
-    assert hooks.ttx_has_test_hooks() == 1 and all(hasattr(hooks, k) for k in knobs)
+    assert hooks.ttx_has_test_hooks() == 1 and all(hasattr(hooks, k) for k in knobs + records)
+    assert set(E.debug_t4_route()) == set(E.T4_ROUTE_FIELDS) and E.lib() is E._product
     # the shim: product library until a knob moves, back when it is reset
     assert E.lib() is E._product and E.lib().ttx_has_test_hooks() == 0
     E.debug_skip(256)

@@ -674,7 +674,9 @@ def test_four_cores_run_on_the_three_core_kernels(q, ranks):
     """Round 4: a T = 4 geometry with q2 q3 <= 16 (q3 <= 8) runs on the shape-specialised three-core kernels -- the last two cores of a
     lookup are contracted first (per lookup, M = core_2[i2] * core_3[i3]: matrix-chain order, a tenth of the multiply-adds the
     reference's left-to-right order spends on core 2), the three-core kernel reads M where it reads core 2's slice, and the
-    backward's d M is turned into the partial rows of cores 2 and 3 (csrc/ttx_tt.hip t4_merge_kernel / t4_unmerge_kernel).
+    backward's d M is turned into the partial rows of cores 2 and 3 (csrc/ttx_tt.hip t4_merge_sorted_kernel / t4_merge_kernel, then
+    t4_grad23_mfma_kernel / t4_grad23_kernel and t4_apply23_kernel; their instantiations and batch-size switches one by one:
+    tests/test_t4_routes_gpu.py).
     Against the oracle (left to right, as the reference) and against the generic kernels; forward, dense / SGD / Adagrad; one and
     three tables, ragged bags, partial groups."""
     import tt_embeddings as E
