@@ -200,6 +200,13 @@ def _load(path):
     L.ttx_cache_carry.argtypes = [i64, vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp]
     # merged bags (per-table batches -> one table-major batch)
     L.ttx_bags_merge.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    # dense member tables (bags over uncompressed rows)
+    L.ttx_dense_bags_forward.argtypes = [i32, i64, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.ttx_dense_bags_backward_workspace_bytes.restype = C.c_size_t
+    L.ttx_dense_bags_backward_workspace_bytes.argtypes = [i64, i64, i32]
+    L.ttx_dense_bags_backward.argtypes = [i32, i32, i64, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, i32, vp, vp, vp,
+                                          vp, vp, sz, vp]
+    L.ttx_dense_bags_info.argtypes = [i32, i64, C.POINTER(i32)]
     return L
 
 
@@ -1367,6 +1374,105 @@ def bags_merge(indices: Sequence[torch.Tensor], offsets: Sequence[Optional[torch
         _check(lib().ttx_bags_merge(ntab, B, drop, a_idx, a_nnz, a_ib, a_off, a_ob, a_L, a_w, a_pad, a_has, int(sentinel),
                                     out_i.data_ptr(), out_o.data_ptr(), None if out_w is None else out_w.data_ptr(), _stream(dev)))
     return out_i, out_o, out_w
+
+
+# ---- dense member tables: bags over uncompressed rows (include/ttx.h "dense member tables"; csrc/ttx_dense.hip) ----
+DENSE_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def _dense_tabs(row_base: Sequence[int], padding: Optional[Sequence[Optional[int]]]):
+    """the host arrays of the dense calls as packed bytes: row_base (num_tables + 1 int64), padding (-1: none) or None"""
+    ntab = len(row_base) - 1
+    a_base = struct.pack(f"{ntab + 1}q", *[int(v) for v in row_base])
+    a_pad = None
+    if padding is not None and any(v is not None for v in padding):
+        if len(padding) != ntab:
+            raise RuntimeError(f"tt_embeddings: dense bags: padding must have one entry per table ({ntab})")
+        a_pad = struct.pack(f"{ntab}q", *[-1 if v is None else int(v) for v in padding])
+    return ntab, a_base, a_pad
+
+
+def _dense_batch(indices, offsets, weight, ntab):
+    dev = _dev(weight)
+    if weight.dtype != torch.float32 or weight.dim() != 2 or not weight.is_contiguous():
+        raise RuntimeError("tt_embeddings: dense bags: weight must be contiguous float32 [R, D]")
+    indices, offsets = _i64(indices, "indices"), _i64(offsets, "offsets")
+    if indices.device != dev or offsets.device != dev:
+        raise RuntimeError(f"tt_embeddings: dense bags: indices and offsets must live on {dev}")
+    nb = offsets.numel() - 1
+    if nb < 0 or nb % ntab:
+        raise RuntimeError(f"tt_embeddings: dense bags: offsets needs num_tables * B + 1 entries ({ntab} tables), got {offsets.numel()}")
+    return dev, indices, offsets, nb // ntab
+
+
+def dense_bags_forward(indices: torch.Tensor, offsets: torch.Tensor, row_base: Sequence[int], weight: torch.Tensor,
+                       mode: str = "sum", padding: Optional[Sequence[Optional[int]]] = None,
+                       per_sample_weights: Optional[torch.Tensor] = None
+                       ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Bags over uncompressed tables, table-major (bag b belongs to table b // B): weight [R, D] holds table k's rows at
+    [row_base[k], row_base[k + 1]).  -> (output [num_tables * B, D], live int32 per bag -- mean only, else None --, argmax int32
+    [num_tables * B, D] -- max only, else None).  A negative index and `padding[table]` are padding; other indices are clamped."""
+    ntab, a_base, a_pad = _dense_tabs(row_base, padding)
+    dev, indices, offsets, B = _dense_batch(indices, offsets, weight, ntab)
+    D, nnz, m = weight.size(1), indices.numel(), DENSE_MODES[mode]
+    psw = None if per_sample_weights is None else _f32(per_sample_weights.detach(), "per_sample_weights").reshape(-1)
+    if psw is not None and psw.numel() != nnz:
+        raise RuntimeError("tt_embeddings: dense bags: per_sample_weights must have one entry per index")
+    out = torch.empty((ntab * B, D), dtype=torch.float32, device=dev)
+    live = torch.empty(ntab * B, dtype=torch.int32, device=dev) if m == 1 else None
+    arg = torch.empty((ntab * B, D), dtype=torch.int32, device=dev) if m == 2 else None
+    with _guard(dev):
+        _check(lib().ttx_dense_bags_forward(ntab, B, D, nnz, indices.data_ptr(), offsets.data_ptr(), a_base, a_pad,
+                                            None if psw is None else psw.data_ptr(), m, weight.data_ptr(), out.data_ptr(),
+                                            None if live is None else live.data_ptr(), None if arg is None else arg.data_ptr(),
+                                            _stream(dev)))
+    return out, live, arg
+
+
+def dense_bags_backward(optim: int, indices: torch.Tensor, offsets: torch.Tensor, row_base: Sequence[int], weight: torch.Tensor,
+                        grad_output: torch.Tensor, mode: str = "sum", padding: Optional[Sequence[Optional[int]]] = None,
+                        per_sample_weights: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None,
+                        argmax: Optional[torch.Tensor] = None, lr: float = 0.0, eps: float = 0.0,
+                        opt_state: Optional[torch.Tensor] = None, want_d_psw: bool = False
+                        ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The backward of dense_bags_forward, one update per touched row, no atomics.  optim OPTIM_SGD / OPTIM_ADAGRAD update `weight`
+    (and `opt_state`: [R, D] element-wise, [R] row-wise) in place; OPTIM_DENSE returns the gradient [R, D].  -> (d_weight or None,
+    d_per_sample_weights [nnz] from the weights before the update, or None unless `want_d_psw`)."""
+    ntab, a_base, a_pad = _dense_tabs(row_base, padding)
+    dev, indices, offsets, B = _dense_batch(indices, offsets, weight, ntab)
+    D, nnz, m = weight.size(1), indices.numel(), DENSE_MODES[mode]
+    grad_output = _f32(grad_output, "grad_output")
+    if grad_output.numel() != ntab * B * D:
+        raise RuntimeError(f"tt_embeddings: dense bags: grad_output must hold [{ntab * B}, {D}], got {tuple(grad_output.shape)}")
+    psw = None if per_sample_weights is None else _f32(per_sample_weights.detach(), "per_sample_weights").reshape(-1)
+    width = 0
+    if optim == OPTIM_ADAGRAD:
+        if opt_state is None or opt_state.dtype != torch.float32 or not opt_state.is_contiguous() or \
+                opt_state.numel() not in (weight.size(0), weight.numel()):
+            raise RuntimeError("tt_embeddings: dense bags: Adagrad needs a contiguous float32 opt_state of [R] or [R, D]")
+        width = D if opt_state.numel() == weight.numel() else 1
+    d_w = torch.empty_like(weight) if optim == OPTIM_DENSE else None
+    d_psw = torch.empty(nnz, dtype=torch.float32, device=dev) if want_d_psw else None
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, lb.ttx_dense_bags_backward_workspace_bytes(ntab * B, nnz, D))
+    with _guard(dev):
+        _check(lb.ttx_dense_bags_backward(optim, ntab, B, D, nnz, indices.data_ptr(), offsets.data_ptr(), a_base, a_pad,
+                                          None if psw is None else psw.data_ptr(), m,
+                                          None if live is None else live.data_ptr(), None if argmax is None else argmax.data_ptr(),
+                                          grad_output.data_ptr(), lr, eps, width,
+                                          opt_state.data_ptr() if width else None, weight.data_ptr(),
+                                          None if d_w is None else d_w.data_ptr(), None if d_psw is None else d_psw.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), st))
+    return d_w, d_psw
+
+
+def dense_bags_info(D: int, nnz: int) -> dict:
+    """host-side query: the sizes at which the dense backward switches behaviour -- `split`: a row with more lookups than this has
+    its list summed in chunks of this length; `one_launch`: the batch size at which a one-launch route hands over (0: none)"""
+    out = (C.c_int32 * 2)()
+    _check(lib().ttx_dense_bags_info(int(D), int(nnz), out))
+    return {"split": int(out[0]), "one_launch": int(out[1])}
 
 
 def profile_enable(mask: int) -> None:

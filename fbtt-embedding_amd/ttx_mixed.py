@@ -27,6 +27,7 @@ from torch import nn
 import tt_embeddings_ops as _ops
 from tt_embeddings_ops import (POOLING_MODES, OptimType, TableBatchedTTEmbeddingBag, _normalise_padding_idx,
                                suggested_tt_shapes)
+from ttx_dense import DenseTableBatchedEmbeddingBag, dense_table_flags, dense_table_groups
 
 
 def merge_bags(indices: Sequence[torch.Tensor], offsets: Sequence[torch.Tensor],
@@ -342,6 +343,11 @@ class MixedTTEmbeddingBag(nn.Module):
     `mode`, `padding_idx` (trailing keywords): nn.EmbeddingBag's pooling modes and padded batches as on the uniform modules
     (DESIGN.md 4.9 - 4.11).  `padding_idx` is None, one int, or one entry (int or None) per table, each normalised against its own
     table's cardinality.
+    `dense_below` / `dense` (trailing keywords): table k stays UNCOMPRESSED when `dense[k]` is true or, without
+    `dense`, when num_embeddings[k] < dense_below.  Those tables form `self.dense_groups` / `self.dense_group_tables` (one
+    `DenseTableBatchedEmbeddingBag` per 64 of them: plain rows, one lookup launch, one update per touched row); `self.groups` /
+    `self.group_tables` keep holding the TT groups only, so the cache fan-outs and the `cache_size` split see TT tables only.  The
+    defaults select no table: same groups, same state_dict() keys, same routes.
     `use_cache=True` (with fused=True): every fused group gets ONE LFU row cache over its tables
     (`VarTableTTEmbeddingBag(use_cache=True)`).  A positive `cache_size` / `hashtbl_size` is the total over the groups, split in
     proportion to their summed cardinalities (rounded down, at least 1 each); 0 gives every group its default.  `cache_populate()`,
@@ -358,7 +364,8 @@ class MixedTTEmbeddingBag(nn.Module):
                  device: Optional[torch.device] = None, include_last_offset: bool = False,
                  streams: bool = False, fused: bool = False, pad_ranks: Optional[bool] = None,
                  pad_q: Optional[bool] = None, mode: str = "sum", padding_idx=None, use_cache: bool = False,
-                 cache_size: int = 0, hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None) -> None:
+                 cache_size: int = 0, hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None,
+                 dense_below: int = 0, dense: Optional[Sequence[bool]] = None) -> None:
         super().__init__()
         if use_cache and not fused:
             raise NotImplementedError("use_cache=True needs fused=True: the row cache is one per fused group "
@@ -369,6 +376,9 @@ class MixedTTEmbeddingBag(nn.Module):
         if mode not in POOLING_MODES:
             raise ValueError(f"mode must be one of {POOLING_MODES}, got {mode!r}")
         self.mode = mode
+        # the tables that stay uncompressed (dense_below / dense) leave the TT grouping below: tt_ids = the others
+        self.dense_tables = dense_table_flags(self.num_embeddings, dense_below, dense)
+        tt_ids = [k for k in range(n) if not self.dense_tables[k]]
         # padding_idx: None, one int for all tables, or one entry (an int or None) per table -- each normalised by torch's rule
         # against its OWN table's cardinality (-1 is every table's last row)
         if isinstance(padding_idx, (list, tuple)):
@@ -409,7 +419,7 @@ class MixedTTEmbeddingBag(nn.Module):
         if pad_q is None and fused:
             # auto: when the padding costs at most twice the tables' own multiply-adds
             by_nd: Dict[int, List[int]] = {}
-            for k in range(n):
+            for k in tt_ids:
                 by_nd.setdefault(len(ranks[k]), []).append(k)
             for tabs in by_nd.values():
                 if len({tuple(qs[k]) for k in tabs}) < 2 or pad_ranks is False and len({tuple(ranks[k]) for k in tabs}) > 1:
@@ -421,7 +431,7 @@ class MixedTTEmbeddingBag(nn.Module):
                 if madds([1] + rmax + [1], qmax) * len(tabs) <= 2 * real:
                     padq_nd.add(nd1)
         elif pad_q and fused:
-            padq_nd = {len(r) for r in ranks}
+            padq_nd = {len(ranks[k]) for k in tt_ids}
         pad_q = bool(padq_nd)
         if pad_ranks is None and fused:
             # auto: one launch set per factoring when the zero padding costs at most twice the tables' own multiply-adds
@@ -429,7 +439,7 @@ class MixedTTEmbeddingBag(nn.Module):
             # [13,12] in one set 0.72 vs 0.43 in four)
             pad_ranks = True
             by_q: Dict[tuple, List[int]] = {}
-            for k in range(n):
+            for k in tt_ids:
                 if len(ranks[k]) in padq_nd:  # (q-padded groups pad their ranks anyway: they do not vote on the others' rule)
                     continue
                 by_q.setdefault((len(ranks[k]), None if qs[k] is None else tuple(qs[k])), []).append(k)
@@ -440,7 +450,7 @@ class MixedTTEmbeddingBag(nn.Module):
                 if madds([1] + rmax + [1], qq) * len(tabs) > 2 * real:
                     pad_ranks = False
         groups: Dict[tuple, List[int]] = {}
-        for k in range(n):
+        for k in tt_ids:
             # fused: tables of one factoring q share a batched lookup whatever their ranks (smaller ranks are zero-padded to the
             # group's largest, VarTableTTEmbeddingBag(table_ranks=)); pad_ranks=False keeps one group per (q, ranks)
             inq = len(ranks[k]) in padq_nd  # this table's core-count group shares ONE padded factoring (ranks padded with it)
@@ -451,7 +461,7 @@ class MixedTTEmbeddingBag(nn.Module):
         self.groups = nn.ModuleList()
         # use_cache: every fused group gets a cache of its own.  A positive cache_size / hashtbl_size is the TOTAL over the groups,
         # split in proportion to the groups' summed cardinalities (rounded down, at least 1 each); 0: every group's own default
-        total_rows = sum(self.num_embeddings)
+        total_rows = sum(self.num_embeddings[k] for k in tt_ids)  # (the TT tables': a dense table has no cache)
         for tables in self.group_tables:
             k0 = tables[0]
             cache_kw = {}
@@ -487,6 +497,12 @@ class MixedTTEmbeddingBag(nn.Module):
                 mod.padding_idx = PAD_SENTINEL
         self._streams = [torch.cuda.Stream(device=self.groups[0].tt_cores[0].device) for _ in self.groups] \
             if streams and len(self.groups) > 1 else None
+        # the uncompressed tables: one DenseTableBatchedEmbeddingBag per 64 of them, in the caller's order; they run on the calling
+        # stream.  A table's padding reaches the kernel as PAD_SENTINEL in the merged batch, which it skips itself.
+        self.dense_group_tables = dense_table_groups(self.dense_tables)
+        self.dense_groups = nn.ModuleList(
+            DenseTableBatchedEmbeddingBag([self.num_embeddings[k] for k in tables], self.embedding_dim, optimizer, learning_rate,
+                                          eps, sparse, device, True, mode) for tables in self.dense_group_tables)
 
     # ------------------------------------------------------------------ the groups' row caches (use_cache=True)
     def cache_populate(self, keep_trained: bool = False, freq_shift: int = 0) -> None:
@@ -592,6 +608,11 @@ class MixedTTEmbeddingBag(nn.Module):
                 res.record_stream(cur)   # ... and the other way round
             else:
                 res = mod(idx, off, True, psw)
+            for j, k in enumerate(tables):
+                outs[k] = res[j]
+        for mod, tables in zip(self.__dict__["_modules"].get("dense_groups", ()), self.__dict__.get("dense_group_tables", ())):
+            idx, off, psw = self._merge(tables, indices, offsets, per_sample_weights)
+            res = mod(idx, off, psw)  # [tables, B, D], on the calling stream
             for j, k in enumerate(tables):
                 outs[k] = res[j]
         if self._streams:

@@ -809,6 +809,50 @@ int ttx_cache_backward_sorted(int32_t optim, int64_t nnz, const int32_t* skip_de
                               float learning_rate, float eps, int64_t cache_size, float* cache_optimizer_state,
                               float* dst, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
 
+/* ---- dense member tables (csrc/ttx_dense.hip; not in the reference) --------------------------------------
+ * Bags over UNCOMPRESSED tables: the small members of a mixed-cardinality module, for which a TT factorisation saves nothing.
+ * weight [R, D] float32 row-major holds the tables' rows one table after the other: table k owns rows [row_base[k], row_base[k + 1]),
+ * R = row_base[num_tables].  row_base is a HOST array of num_tables + 1 int64 read during the call (it travels in the kernel
+ * arguments, as key_base does in ttx_table_keys_v); num_tables <= TTX_MAX_TABLES_MIXED.  The batch is the table-major form of the
+ * batched modules: indices [nnz] int64, offsets [num_tables * B + 1] int64, bag b belongs to table b / B.
+ * CONTRACT
+ *   padding     a slot is padding when its index is negative (the merged batches' sentinel -1), or when padding != NULL and the
+ *               index equals padding[table] (HOST array, num_tables int64, a negative entry: the table has none).  Every other
+ *               index is clamped into [0, E_k - 1] before it addresses anything: another row, never out of bounds.
+ *   forward     mode 0 sum (per_sample_weights optional), 1 mean (divisor = the bag's count of non-padding slots, left in
+ *               live[bag]), 2 max (strict > in position order: the first position wins a tie; argmax [num_tables * B, D] = the
+ *               winning position n, -1 for a bag without a live slot -- as ttx_bag_max_pool).  A bag without a live slot gives
+ *               zeros.  Every output element has one writer: no memset in front.
+ *   backward    row r's gradient G_r = sum over r's live lookups n, in index order, of c_n * grad_output[bag(n)] (sum: the weight;
+ *               mean: 1 / live; max: column e counts where argmax[bag(n), e] == n), lists longer than the split length of
+ *               ttx_dense_bags_info summed per chunk and the chunk sums added in chunk order.  Applied ONCE per touched row:
+ *               TTX_OPTIM_SGD w -= lr G; TTX_OPTIM_ADAGRAD with state_width == D (opt_state [R, D]) s += G^2, w -= lr G / (sqrt(s) + eps);
+ *               with state_width == 1 (opt_state [R]) s_r += mean_e(G_e^2), w -= lr G / (sqrt(s_r) + eps); TTX_OPTIM_DENSE
+ *               (state_width 0) d_weight[r] = G_r and zeros for every other row (the call writes every element of d_weight).
+ *               d_per_sample_weights (NULL or [nnz], mode 0): <grad_output[bag(n)], weight[row(n)]> from the weights as they were
+ *               BEFORE this call's update, 0 at padding.  No float atomics, one writer per row: bit-identical from run to run.
+ *   paths       16-byte accesses when D % 4 == 0 and every float / int32 pointer is 16-byte aligned, a scalar path otherwise;
+ *               rows wider than 256 floats are walked per column block; offsets are 64-bit.
+ *   capture     nothing is read back to the host, nothing is allocated: both calls are capturable.
+ *   errors      -1 with ttx_last_error() set, before anything touches a device: a negative size, nnz or num_tables * B >= 2^31,
+ *               num_tables outside [1, TTX_MAX_TABLES_MIXED], row_base NULL / not starting at 0 / not strictly increasing,
+ *               D <= 0, state_width not in {0, 1, D} or not matching optim, weights with a mode other than 0, argmax / live
+ *               missing where the mode needs it, a NULL or misaligned pointer that would be used; TTX_EWORKSPACE for a workspace
+ *               that is too small.  nnz == 0 still writes the zero output (and d_weight under DENSE) and trains nothing.
+ * ttx_dense_bags_info (host-side, stateless): out[2] = {the list length beyond which a row's lookups are split into chunks of
+ * that length, the batch size at which a one-launch route hands over -- 0: there is none, every batch takes the sorted route}. */
+int ttx_dense_bags_forward(int32_t num_tables, int64_t B, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* offsets,
+                           const int64_t* row_base, const int64_t* padding, const float* per_sample_weights, int32_t mode,
+                           const float* weight, float* output, int32_t* live, int32_t* argmax, ttx_stream_t stream);
+size_t ttx_dense_bags_backward_workspace_bytes(int64_t num_bags, int64_t nnz, int32_t D);
+int ttx_dense_bags_backward(int32_t optim, int32_t num_tables, int64_t B, int32_t D, int64_t nnz, const int64_t* indices,
+                            const int64_t* offsets, const int64_t* row_base, const int64_t* padding,
+                            const float* per_sample_weights, int32_t mode, const int32_t* live, const int32_t* argmax,
+                            const float* grad_output, float lr, float eps, int32_t state_width, float* opt_state, float* weight,
+                            float* d_weight, float* d_per_sample_weights, void* workspace, size_t workspace_bytes,
+                            ttx_stream_t stream);
+int ttx_dense_bags_info(int32_t D, int64_t nnz, int32_t* out);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
