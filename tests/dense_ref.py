@@ -68,6 +68,79 @@ def row_grads(weight, indices, offsets, row_base, B, d_out, mode="sum", padding=
     return G, touched, d_psw
 
 
+# ---- the same three, vectorised ------------------------------------------------------------------------------------------------
+# The loop forms above are the definition.  The forms below restate them with array operations for batches beyond ~20 k lookups,
+# and add every contribution in the SAME order (np.add.at applies its operands one after the other, in index order), so they are
+# bit for bit equal to the loop forms in float64 and in float32 -- the "plain sum in index order" yardstick included, in every
+# mode.  tests/test_dense_tables_cpu.py pins that on every case of tests/dense_cases.py below 20 k lookups.  They need what the
+# kernels' bag search needs: offsets that, clamped into [0, nnz], do not decrease.
+def lookups_vec(indices, offsets, row_base, B, padding=None):
+    indices, offsets = np.asarray(indices, np.int64), np.asarray(offsets, np.int64)
+    row_base = np.asarray(row_base, np.int64)
+    nnz, nb = indices.size, offsets.size - 1
+    cs = np.clip(offsets, 0, nnz)
+    assert nb < 1 or (np.diff(cs) >= 0).all(), "lookups_vec: the clamped offsets must not decrease (use lookups)"
+    n = np.arange(nnz, dtype=np.int64)
+    if nb < 1:
+        return np.full(nnz, -1, np.int64), np.full(nnz, -1, np.int64)
+    b = np.searchsorted(cs, n, side="right") - 1  # the last b with offsets[b] <= n
+    covered = (b >= 0) & (b < nb)
+    covered &= n < cs[np.clip(b + 1, 0, nb)]
+    bag = np.where(covered, b, -1)
+    t = np.where(covered, b, 0) // max(int(B), 1)
+    base, E = row_base[t], row_base[t + 1] - row_base[t]
+    pad = np.full(len(row_base) - 1, -1, np.int64)
+    if padding is not None:
+        pad = np.asarray([-1 if v is None else int(v) for v in padding], np.int64)
+    live = covered & (indices >= 0) & (indices != pad[t])
+    row = np.where(live, base + np.minimum(indices, E - 1), -1)
+    return bag, row
+
+
+def forward_vec(weight, indices, offsets, row_base, B, mode="sum", padding=None, psw=None, dtype=np.float64):
+    w = np.asarray(weight, dtype)
+    nb, D = len(offsets) - 1, w.shape[1]
+    bag, row = lookups_vec(indices, offsets, row_base, B, padding)
+    n = np.flatnonzero((bag >= 0) & (row >= 0))
+    b, v = bag[n], w[row[n]]
+    out, arg = np.zeros((nb, D), dtype), np.full((nb, D), -1, np.int64)
+    live = np.bincount(b, minlength=nb).astype(np.int64)
+    if mode == "max":
+        top = np.full((nb, D), -np.inf, dtype)
+        np.maximum.at(top, b, v)
+        first = np.full((nb, D), len(bag), np.int64)  # the first position that holds the bag's maximum (strict > in the loop form)
+        np.minimum.at(first, b, np.where(v == top[b], n[:, None], len(bag)))
+        has = (live > 0)[:, None]
+        out, arg = np.where(has, top, dtype(0.0)), np.where(has, first, -1)
+    else:
+        x = np.ones(len(n), dtype) if psw is None else np.asarray(psw).reshape(-1)[n].astype(dtype)
+        np.add.at(out, b, v * x[:, None])
+    if mode == "mean":
+        out /= np.maximum(live, 1)[:, None].astype(dtype)
+    return out, live, arg
+
+
+def row_grads_vec(weight, indices, offsets, row_base, B, d_out, mode="sum", padding=None, psw=None, dtype=np.float64):
+    w, d = np.asarray(weight, dtype), np.asarray(d_out, dtype).reshape(len(offsets) - 1, -1)
+    bag, row = lookups_vec(indices, offsets, row_base, B, padding)
+    _, live, arg = forward_vec(weight, indices, offsets, row_base, B, mode, padding, psw)
+    n = np.flatnonzero((bag >= 0) & (row >= 0))
+    b, r = bag[n], row[n]
+    G, touched, d_psw = np.zeros_like(w), np.zeros(w.shape[0], bool), np.zeros(len(bag), dtype)
+    touched[r] = True
+    if mode == "max":
+        add = np.where(arg[b] == n[:, None], d[b], dtype(0.0))
+    elif mode == "mean":
+        add = d[b] / live[b].astype(dtype)[:, None]
+    else:
+        x = np.ones(len(n), dtype) if psw is None else np.asarray(psw).reshape(-1)[n].astype(dtype)
+        add = d[b] * x[:, None]
+    np.add.at(G, r, add)
+    if len(n):  # (a stack of [1, D] @ [D, 1] products: the dot routine that `d[b] @ w[r]` calls, once per lookup)
+        d_psw[n] = np.matmul(d[b][:, None, :], w[r][:, :, None]).reshape(-1)
+    return G, touched, d_psw
+
+
 def sgd(weight, G, touched, lr):
     w = np.asarray(weight, np.float64).copy()
     w[touched] -= lr * G[touched]

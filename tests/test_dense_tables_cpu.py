@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import dense_cases as DC
 import dense_ref as DR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,6 +123,249 @@ def test_reference_rowwise_adagrad_by_hand():
 def test_reference_clamps_bad_indices_into_their_table():
     bag, row = DR.lookups(np.array([5, -7, 99]), np.array([0, 1, 2, 3]), np.array([0, 3, 4, 28]), 1)
     assert row.tolist() == [2, -1, 27]
+
+
+# ------------------------------------------------------------------------- the mirror of the host-side choices, and the cases
+with open(os.path.join(ROOT, "fbtt-embedding_amd", "csrc", "ttx_dense.hip")) as f:
+    SRC = f.read()
+SQ = re.sub(r"\s+", "", re.sub(r"//[^\n]*", "", re.sub(r"\\\n", "", SRC)))  # (macro continuations joined, comments and spaces out)
+UPDATE = "update tests/dense_cases.py (the mirror and the case table of tests/test_dense_shapes_gpu.py)"
+
+
+def _const(name, text=SRC):
+    m = re.findall(rf"constexpr int {name} = (\d+);", text)
+    assert len(m) == 1, f"{name}: {len(m)} definitions"
+    return int(m[0])
+
+
+def _has(text, what, count=1):
+    assert SQ.count(re.sub(r"\s+", "", text)) == count, f"{what} is no longer `{text}`: {UPDATE}"
+
+
+C_SRC = _const("kDenseSplit")
+
+
+def test_mirror_of_the_host_side_choices():
+    """tests/dense_cases.py restates the constants and host functions of csrc/ttx_dense.hip that decide which path a batch takes;
+    a retuned constant fails here and names the case table to update"""
+    with open(os.path.join(ROOT, "fbtt-embedding_amd", "csrc", "ttx_internal.h")) as f:
+        assert _const("kWave", f.read()) == DC.WAVE
+    with open(os.path.join(ROOT, "include", "ttx.h")) as f:
+        assert re.findall(r"^#define TTX_MAX_TABLES_MIXED (\d+)\b", f.read(), flags=re.M) == [str(DC.MAX_TABLES)]
+    assert _const("kDenseSplit") == DC.SPLIT and _const("kDenseFlight") == DC.FLIGHT and _const("kDT") == DC.THREADS, UPDATE
+    _has("constexpr int kDW = kDT / kWave;", "waves per work-group")
+    _has("constexpr int kDenseBases = TTX_MAX_TABLES_MIXED + 1;", "the staged row bases")
+    # dense_row_grad: CHUNKS_PER_TRIP chunk sums per trip
+    n = DC.CHUNKS_PER_TRIP
+    _has(f"for (long long j = i; j < nnz; j += {n} * kDenseSplit) {{", "dense_row_grad's chunk stride")
+    _has(f"float v[{n}][W]; bool more = true; #pragma unroll for (int u = 0; u < {n}; ++u) {{ const long long jj = j + (long long)u * "
+         "kDenseSplit;", "dense_row_grad's chunks in flight")
+    _has("for (long long j = i; j < end; j += kDenseFlight) {", "dense_list_sum's stride")
+    # the forward: FWD_SLOTS_IN_FLIGHT slots of a row group per trip, the grid cap and the stride behind it
+    _has(f"for (long long j = s + grp; j < e; j += {DC.FWD_SLOTS_IN_FLIGHT} * G) {{", "the forward's slot stride")
+    _has("const int LPR = 1 << lpr_log2, G = kWave >> lpr_log2;", "the forward's lane layout")
+    _has("const long long want = (nb + kDW - 1) / kDW; const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);",
+         "the forward's grid cap")
+    assert DC.FWD_GRID_BAGS == 4096 * (DC.THREADS // DC.WAVE)
+    _has("for (long long bag = (long long)blockIdx.x * kDW + threadIdx.x / kWave; bag < nb; bag += (long long)gridDim.x * kDW) {",
+         "the forward's grid stride")
+    _has("const long long want = (nnz + kDT - 1) / kDT; hipLaunchKernelGGL(dense_keys_kernel, dim3((unsigned)(want < 8192 ? want : "
+         "8192)), dim3(kDT),", "the key kernel's grid cap")
+    assert DC.KEYS_GRID_POSITIONS == 8192 * DC.THREADS
+    _has("for (long long n = (long long)blockIdx.x * kDT + threadIdx.x; n < nnz; n += (long long)gridDim.x * kDT) {",
+         "the key kernel's grid stride")
+    # the three host functions
+    _has("static int dense_sort_passes(int64_t R) { int bits = 0; while (bits < 64 && ((uint64_t)R >> bits)) ++bits; "
+         "return bits < 8 ? 1 : (bits + 7) / 8; }", "dense_sort_passes")
+    _has("sort_pairs_desc(nnz, keys, vals, sort_ws, &ks, &vs, st, dense_sort_passes(R));", "the sort's pass count")
+    _has("const int64_t R = row_base[num_tables];", "the largest key")
+    assert [DC.sort_passes(r) for r in (1, 127, 128, 255, 256, 65535, 65536, 140000, (1 << 24) - 1, 1 << 24)] == \
+        [1, 1, 1, 1, 2, 2, 3, 3, 3, 4]
+    _has("static int dense_lanes_log2(int DV) { int l = 0; while ((1 << l) < DV && (1 << l) < kWave) ++l; return l; }", "dense_lanes_log2")
+    assert [DC.lanes_log2(v) for v in (1, 2, 3, 4, 16, 25, 33, 64, 65, 512)] == [0, 1, 2, 2, 4, 5, 6, 6, 6, 6]
+    _has("static bool dense_vec4(int32_t D, std::initializer_list<const void*> ptrs) { if (D % 4 != 0) return false; "
+         "for (const void* p : ptrs) if (((uintptr_t)p) & 15) return false; return true; }", "dense_vec4")
+    _has("const bool v4 = dense_vec4(D, {weight, output, mode == 2 ? (const void*)argmax : nullptr});", "the forward's 16-byte rule")
+    _has("const bool v4 = dense_vec4(D, {grad_output, target, part, mode == 2 ? (const void*)argmax : nullptr, "
+         "opt == 1 ? (const void*)opt_state : nullptr, d_per_sample_weights ? (const void*)weight : nullptr});",
+         "the backward's 16-byte rule (per call: grad_output and the element-wise state decide it too)")
+    _has("const int DV = v4 ? D / 4 : D, lg = dense_lanes_log2(DV);", "the lane layout", count=2)
+    assert [DC.layout(d) for d in (1, 2, 4, 8, 64, 65, 100, 256, 512)] == \
+        [(1, 1, 1, 64), (1, 2, 2, 32), (4, 1, 1, 64), (4, 2, 2, 32), (4, 16, 16, 4), (1, 65, 64, 1), (4, 25, 32, 2), (4, 64, 64, 1),
+         (4, 128, 64, 1)]
+    assert DC.layout(64, aligned=False) == (1, 64, 64, 1)
+
+
+SMALL = 20000  # lookups: below, the loop forms of dense_ref are quick enough to be run next to the vectorised ones
+
+
+@pytest.mark.parametrize("name", DC.OLD_CASES + DC.NEW_CASES)
+def test_vectorised_reference_is_the_loop_reference_bit_for_bit(name):
+    """every existing case and every new one below 20 k lookups, in the three modes, in float64 and as the fp32 yardstick"""
+    c = DC.case(name, C_SRC)
+    if c["idx"].size >= SMALL:
+        assert name in ("fwd_stride_workload",), f"{name}: {c['idx'].size} lookups"
+        return
+    a = (c["idx"], c["off"], c["base"], c["B"])
+    for x, y in zip(DR.lookups(*a, c["pads"]), DR.lookups_vec(*a, c["pads"])):
+        assert np.array_equal(x, y)
+    for mode in ("sum", "mean", "max"):
+        psw = c["psw"] if mode == "sum" else None
+        for dtype in (np.float64, np.float32):
+            for loop, vec, more in ((DR.forward, DR.forward_vec, ()), (DR.row_grads, DR.row_grads_vec, (c["d_out"],))):
+                want = loop(c["w"], *a, *more, mode, c["pads"], psw, dtype=dtype)
+                got = vec(c["w"], *a, *more, mode, c["pads"], psw, dtype=dtype)
+                for k, (x, y) in enumerate(zip(want, got)):
+                    assert x.dtype == y.dtype and x.shape == y.shape, (mode, dtype, loop.__name__, k)
+                    assert np.array_equal(x, y), (mode, dtype, loop.__name__, k, float(np.abs(x - y).max()))
+
+
+def _window_shared_by_two_chunk_starts(ks, heads, lens, C):
+    """aligned windows of C sorted positions that hold the start of a split run's short last chunk AND of the next run's first
+    full chunk (dense_slot's two workspace rows per window)"""
+    found = []
+    for h, L, h2, L2 in zip(heads[:-1], lens[:-1], heads[1:], lens[1:]):
+        if L > C and L % C and L2 > C and h + L == h2 and (h + L - L % C) // C == h2 // C:
+            found.append(int(h2 // C))
+    return found
+
+
+def test_new_cases_reach_what_they_are_for():
+    """every numbered gap of the suite before tests/test_dense_shapes_gpu.py, by a quantity computed from numpy alone: keys as
+    dense_keys_kernel defines them, a stable descending sort, the mirror of the host-side choices"""
+    C, T = C_SRC, DC.CHUNKS_PER_TRIP
+    old = [DC.case(n, C) for n in DC.OLD_CASES]
+    old_longest = max(int(DC.runs(c)[2].max()) for c in old if DC.runs(c)[2].size)
+    assert old_longest <= T * C, "(what the earlier cases stop at: a run of four chunks)"
+    # 1. runs longer than four chunks: the ladder's hot row is row 0 of table 0 (key 1), exactly k C + m lookups long
+    trips = {}
+    for k in DC.LADDER:
+        c = DC.case(f"ladder_{k}", C)
+        key, head, length = DC.runs(c)
+        L = int(k.split("_")[0]) * C + int(k.split("_")[1])
+        assert key[-1] == 1 and length[-1] == L and head[-1] + L == c["idx"].size, "the smallest key: its run ends at nnz"
+        trips[k] = -(-(-(-L // C)) // T)  # trips of dense_row_grad's loop over ceil(L / C) chunks
+    assert trips == {"3_0": 1, "4_-1": 1, "4_0": 1, "4_1": 2, "5_0": 2, "8_0": 2, "8_1": 3, "40_7": 11}
+    c = DC.case("ladder6_4_1", C)
+    assert DC.runs(c)[2][-1] == 4 * C + 1 and DC.layout(c["D"])[0] == 1, "the scalar backward over a run of two trips"
+    # ... and the run's last chunk counts in every mode: in max mode a lookup adds only the columns it won in its bag, and
+    # a bag's later lookups of the same row win none (the first position keeps a tie)
+    for name in [f"ladder_{k}" for k in DC.LADDER] + ["ladder6_4_1"]:
+        c = DC.case(name, C)
+        _, order = DC.sorted_keys(c)
+        L = int(DC.runs(c)[2][-1])
+        last = order[c["idx"].size - ((L - 1) % C + 1):]  # the positions n of the last chunk's lookups
+        bag, _ = DR.lookups_vec(c["idx"], c["off"], c["base"], c["B"], c["pads"])
+        arg = DR.forward_vec(c["w"], c["idx"], c["off"], c["base"], c["B"], "max")[2]
+        assert any((arg[bag[n]] == n).any() for n in last), f"{name}: the last chunk's lookups win no column in max mode"
+    assert np.log2(DC.runs(DC.case("ladder_40_7", C))[2][-1]) > 10, "the partial kernel's search for a head: more than 10 steps deep"
+    # 2. where a split run sits
+    def hot_runs(name):
+        c = DC.case(name, C)
+        key, head, length = DC.runs(c)
+        ks, _ = DC.sorted_keys(c)
+        at = {int(k): (int(h), int(n)) for k, h, n in zip(key, head, length)}
+        for k, L in c["hot"].items():
+            assert at[k][1] == L, (name, k)
+        return c, ks, key, head, length, [at[k] for k in sorted(c["hot"], reverse=True)]
+
+    c, ks, key, head, length, hot = hot_runs("place_first")
+    assert hot == [(0, 4 * C + 1)] and ks[0] == c["base"][-1], "the largest key: a split run at sorted position 0"
+    c, ks, key, head, length, hot = hot_runs("place_middle")
+    (h, L), = hot
+    assert h > 0 and ks[h - 1] > ks[h] and h + L < ks.size and 0 < ks[h + L] < ks[h] and L == 4 * C + 1, "between other runs"
+    c, ks, key, head, length, hot = hot_runs("place_row0_padded")
+    (h, L), = hot
+    assert ks[h] == 1 and L == 4 * C + 1 and h + L < ks.size and not ks[h + L:].any(), "the key-0 tail of padding behind the run"
+    assert (c["idx"] == -1).any() and (c["idx"][:c["off"][c["B"]]] == 2).any(), "the sentinel and table 0's padding value"
+    for name, want in (("place_two", [4 * C + 1, 2 * C]), ("place_three", [4 * C + 1, 2 * C, C + 1])):
+        c, ks, key, head, length, hot = hot_runs(name)
+        assert [L for _, L in hot] == want and all(a[0] + a[1] == b[0] for a, b in zip(hot, hot[1:])), "split runs back to back"
+        shared = _window_shared_by_two_chunk_starts(ks, head, length, C)
+        assert hot[1][0] // C in shared, f"{name}: no window of {C} positions holds a last chunk's and a first chunk's start"
+    # 3. the sort's pass count, on both sides of each digit boundary
+    passes = {}
+    for name in DC.BOUNDARIES:
+        c = DC.case(name, C)
+        R = int(c["base"][-1])
+        key, head, length = DC.runs(c)
+        passes[name] = DC.sort_passes(R)
+        assert key[0] == R and key[-1] == 1 and c["D"] == 8 and c["B"] <= 8, "the last row (key R) and row 0"
+        # one pass fewer sorts by the low digits only: the case must hold keys that then fall into one another's runs
+        if passes[name] > 1:
+            _, row = DR.lookups_vec(c["idx"], c["off"], c["base"], c["B"], c["pads"])
+            k = row + 1
+            kl = k & ((1 << (8 * (passes[name] - 1))) - 1)
+            o = np.argsort(-kl, kind="stable")
+            n_runs = int((np.diff(k[o]) != 0).sum()) + 1
+            assert n_runs > np.unique(k).size, f"{name}: a sort of {passes[name] - 1} pass(es) would still leave every row one run"
+    assert passes == {"rows_255": 1, "rows_256": 2, "rows_65535": 2, "rows_65536": 3, "three_pass": 3}
+    assert {DC.sort_passes(int(c["base"][-1])) for c in old} <= {1, 2}
+    c = DC.case("three_pass", C)
+    assert c["Es"] == [70000, 70000] and {6, 65542, 70006, 135542} <= set(DC.runs(c)[0].tolist()), "keys that differ in bits 16 and up"
+    # 4. more than four tables
+    for name in DC.TABLES:
+        c = DC.case(name, C)
+        nt = len(c["Es"])
+        assert nt == int(name.split("_")[1]) and c["B"] == 3 and set(c["Es"]) <= set(range(1, 8)) and c["pads"][-1] is not None
+        _, row = DR.lookups_vec(c["idx"], c["off"], c["base"], c["B"], c["pads"])
+        tab = np.searchsorted(c["base"], row[row >= 0], side="right") - 1
+        assert set(tab.tolist()) == set(range(nt)), "every table receives live lookups"
+        held = [t for t in range(nt) if c["pads"][t] is not None and
+                (c["idx"][c["off"][3 * t]:c["off"][3 * t + 3]] == c["pads"][t]).any()]
+        assert len(held) >= min(3, nt // 3) and nt - 1 in held, "padding values on several tables, the last included"
+    assert len(DC.case("tables_64", C)["Es"]) == DC.MAX_TABLES and max(len(c["Es"]) for c in old) == 4
+    # 5. the grid-stride loops
+    for name, nb in (("fwd_stride_d4", 64 * 257), ("fwd_stride_workload", 16 * 2048)):
+        c = DC.case(name, C)
+        assert len(c["off"]) - 1 == nb > DC.FWD_GRID_BAGS, "a wave of the forward takes more than one bag"
+    lens = np.diff(DC.case("fwd_stride_d4", C)["off"])
+    assert lens.min() == 0 and lens.max() == 2 and np.diff(DC.case("fwd_stride_workload", C)["off"]).min() == 1
+    assert max(len(c["off"]) - 1 for c in old) <= DC.FWD_GRID_BAGS and max(c["idx"].size for c in old) <= DC.KEYS_GRID_POSITIONS
+    assert DC.KEYS_NNZ == (1 << 21) + 300 > DC.KEYS_GRID_POSITIONS and DC.KEYS_SMALL // 3 > 1000 * C
+    # 6. lane layouts: lanes per row, row groups per wave, slots per trip of the forward's loop against the 300-slot bag
+    seen = {}
+    for D in DC.WIDTHS:
+        c = DC.case(f"width_{D}", C)
+        W, DV, LPR, G = DC.layout(D)
+        seen[D] = (W, LPR, G, -(-DV // LPR))
+        assert c["B"] == 5 and np.diff(c["off"]).max() == 300 > DC.FWD_SLOTS_IN_FLIGHT * G, "a second trip of the slot loop"
+        s = int(c["off"][2 * 5])
+        assert c["idx"][s] == c["idx"][s + 1], "the tie table: a bag's first two slots hold the same row"
+    assert seen == {1: (1, 1, 64, 1), 2: (1, 2, 32, 1), 4: (4, 1, 64, 1), 8: (4, 2, 32, 1), 65: (1, 64, 1, 2), 100: (4, 32, 2, 1),
+                    256: (4, 64, 1, 1), 512: (4, 64, 1, 2)}, "(W, lanes per row, row groups, column blocks)"
+    assert not {DC.layout(c["D"], not c.get("misaligned"))[:3] for c in old} & {seen[d][:3] for d in (1, 4, 8, 100)}
+    # 7. a 16-byte forward with a scalar backward is a flag of the case; the GPU test asserts the pointers' alignment
+    assert DC.case("misaligned_d_out", C)["D"] == 64 and DC.case("misaligned_state", C)["D"] == 64
+    # 8. offsets that do not tile indices
+    for name, last in (("offsets_short", -4), ("offsets_beyond", 5)):
+        c = DC.case(name, C)
+        nnz = c["idx"].size
+        bag, row = DR.lookups_vec(c["idx"], c["off"], c["base"], c["B"], c["pads"])
+        assert c["off"][0] == 3 and c["off"][-1] == nnz + last and (bag[:3] == -1).all() and (bag[3:nnz + min(last, 0)] >= 0).all()
+        assert (bag[nnz + min(last, 0):] == -1).all() and ((bag >= 0) & (row < 0)).any(), "uncovered positions, and padding"
+        assert (c["idx"][bag < 0] >= 0).any(), "an uncovered position holds a live index: it must contribute nothing"
+    assert all(c["off"][0] == 0 and c["off"][-1] == c["idx"].size for c in old)
+
+
+@pytest.mark.parametrize("name", DC.NEW_CASES + DC.LARGE_CASES)
+def test_yardstick_of_every_new_case_stays_under_the_cap(name):
+    """The widening rule (twice the plain-fp32 index-order sum's distance from float64) is capped at 5 default bounds; the cap is a
+    condition on the case, not a measurement: a case whose yardstick needs more is reshaped (fewer lookups of a row)."""
+    import tt_ref64 as R64
+
+    c = DC.case(name, C_SRC)
+    for mode in c.get("modes", ("sum", "mean", "max")):
+        psw = c["psw"] if mode == "sum" else None
+        a = (c["w"], c["idx"], c["off"], c["base"], c["B"])
+        out = DR.forward_vec(*a, mode, c["pads"], psw)[0]
+        out32 = DR.forward_vec(*a, mode, c["pads"], psw, dtype=np.float32)[0]
+        G, _, dp = DR.row_grads_vec(*a, c["d_out"], mode, c["pads"], psw)
+        G32, _, dp32 = DR.row_grads_vec(*a, c["d_out"], mode, c["pads"], psw, dtype=np.float32)
+        for what, x32, x in (("forward", out32, out), ("G", G32, G), ("d_psw", dp32, dp)):
+            u = R64.default_units(x32, x)
+            print(f"[dense-tables] {name} {mode} {what}: plain fp32 {u:.3f} default bounds from float64")
+            assert 2.0 * u <= R64.WIDEN_CAP, (name, mode, what, u)
 
 
 # ----------------------------------------------------------------------------------------------------------------- the ABI

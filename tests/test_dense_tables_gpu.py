@@ -7,9 +7,10 @@ tests/test_fused_optimizer_gpu.py: when a plain fp32 numpy sum in index order of
 itself more than half a default bound from float64, twice that distance is allowed, capped at (5e-5, 1e-5)
 (tt_ref64.widen_factor).  Every figure is printed (pytest -s).  The updated weights are bounded by the gradient's bound carried
 through the update: SGD is linear in G (lr dG); element-wise Adagrad as util.assert_adagrad_close(state0=, scale=) derives it; the
-row-wise form by the same derivative with the row's state (rowwise_bound below)."""
-import functools
+row-wise form by the same derivative with the row's state (dense_check.rowwise_bound).
 
+The cases are built by tests/dense_cases.py, the comparison itself is tests/dense_check.py::check_kernels, which
+tests/test_dense_shapes_gpu.py runs on the shapes of the measured workload."""
 import numpy as np
 import pytest
 import torch
@@ -17,234 +18,18 @@ import torch.nn.functional as F
 
 import dense_ref as DR
 import tt_ref64 as R64
+from dense_cases import ES, OLD_CASES as CASES, PADS
+from dense_check import (DEV, assert_within, case, check_kernels, dev_weight, eng, grad_bound, own_bound, reference,  # noqa: F401
+                         split_len)
 from util import ATOL_SCALE, EPS, LR, RTOL, assert_adagrad_close, assert_close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-ES = [3, 1, 24, 1460]
-PADS = [2, None, 5, 0]
-
-
-def eng():
-    import tt_embeddings as E
-
-    return E
-
-
-def split_len():
-    return eng().dense_bags_info(64, 1000)["split"]
-
-
-def _split_case(L, D):
-    """tables [3, 24], B = 37: row 0 of table 0 is looked up exactly L times, its lookups spread over the bags between others"""
-    rs = np.random.RandomState(L)
-    B, idx, off = 37, [], [0]
-    per = [L // B + (1 if b < L % B else 0) for b in range(B)]
-    for b in range(B):
-        bag = [0] * per[b] + rs.randint(1, 3, size=2).tolist()
-        rs.shuffle(bag)
-        idx += bag
-        off.append(len(idx))
-    for b in range(B):
-        idx += rs.randint(0, 24, size=int(rs.randint(0, 4))).tolist()
-        off.append(len(idx))
-    idx = np.asarray(idx, np.int64)
-    assert int((idx[:off[B]] == 0).sum()) == L
-    return dict(Es=[3, 24], B=B, D=D, idx=idx, off=np.asarray(off, np.int64), pads=None,
-                psw=rs.uniform(0.5, 1.5, size=idx.size).astype(np.float32))
-
-
-def _general(D, B, seed, **kw):
-    idx, off, psw = DR.make_batch(seed, ES, B, pad=PADS, **kw)
-    return dict(Es=ES, B=B, D=D, idx=idx, off=off, psw=psw, pads=PADS)
-
-
-@functools.lru_cache(maxsize=None)
-def case(name):
-    C = split_len()
-    if name == "split_scalar":
-        c = _split_case(C + 1, 6)
-    elif name.startswith("split"):  # split_<k>_<0|1>: a row with exactly k * C + (0 | 1) lookups
-        _, k, more = name.split("_")
-        c = _split_case(int(k) * C + int(more), 64)
-    elif name == "d64":  # the 16-byte path; a bag of 70 slots (more than the rows in flight); table 2 receives no lookup
-        c = _general(64, 37, 1, tie_table=3, silent_table=2, long_bag=(3, 5, 70))
-    elif name == "d64_b1":
-        c = _general(64, 1, 2, tie_table=3, empty=0)
-    elif name == "d64_misaligned":  # a weight view one float off a 16-byte boundary: the scalar path at D = 64
-        c = dict(_general(64, 5, 3, tie_table=2), misaligned=True)
-    elif name == "d6":
-        c = _general(6, 37, 4, tie_table=2, long_bag=(2, 7, 70))
-    elif name == "d3_b1":
-        c = _general(3, 1, 5, tie_table=3, empty=0)
-    elif name == "d260":  # rows wider than 256 floats: the column-block walk
-        c = _general(260, 5, 6, tie_table=2, long_bag=(3, 2, 70))
-    elif name == "nnz0":
-        c = dict(Es=ES, B=4, D=64, idx=np.zeros(0, np.int64), off=np.zeros(17, np.int64), psw=np.zeros(0, np.float32), pads=PADS)
-    elif name == "all_padding":  # the tables' padding values and the merged batches' sentinel, nothing else
-        B = 4
-        idx = np.concatenate([np.full(2 * B, 2), np.full(2 * B, -1), np.full(2 * B, 5), np.full(2 * B, 0)]).astype(np.int64)
-        c = dict(Es=ES, B=B, D=64, idx=idx, off=np.arange(0, 8 * B + 1, 2, dtype=np.int64), pads=PADS,
-                 psw=np.ones(idx.size, np.float32))
-    else:
-        raise KeyError(name)
-    c = dict(c)
-    c["base"] = np.concatenate([[0], np.cumsum(c["Es"])]).astype(np.int64)
-    R = int(c["base"][-1])
-    rs = np.random.RandomState(77)
-    c["w"] = rs.uniform(-1, 1, size=(R, c["D"])).astype(np.float32)
-    c["d_out"] = rs.standard_normal((len(c["off"]) - 1, c["D"])).astype(np.float32)
-    # a live, all-distinct Adagrad state
-    c["s_elem"] = (0.5 + 1e-4 * np.arange(R * c["D"])).reshape(R, c["D"]).astype(np.float32)
-    c["s_row"] = (0.5 + 1e-3 * np.arange(R)).astype(np.float32)
-    assert np.unique(c["s_elem"]).size == c["s_elem"].size and np.unique(c["s_row"]).size == R
-    return c
-
-
-CASES = ["d64", "d64_b1", "d64_misaligned", "d6", "d3_b1", "d260", "split_1_0", "split_1_1", "split_2_0", "split_2_1",
-         "split_scalar", "nnz0", "all_padding"]
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name, mode):
-    """float64 and plain-fp32 results of (case, mode), computed once and shared"""
-    c = case(name)
-    psw = c["psw"] if mode == "sum" else None
-    a = (c["w"], c["idx"], c["off"], c["base"], c["B"])
-    out, live, arg = DR.forward(*a, mode, c["pads"], psw)
-    out32, _, _ = DR.forward(*a, mode, c["pads"], psw, dtype=np.float32)
-    G, touched, d_psw = DR.row_grads(*a, c["d_out"], mode, c["pads"], psw)
-    G32, _, d_psw32 = DR.row_grads(*a, c["d_out"], mode, c["pads"], psw, dtype=np.float32)
-    return dict(out=out, live=live, arg=arg, out32=out32, G=G, touched=touched, d_psw=d_psw, G32=G32, d_psw32=d_psw32, psw=psw)
-
-
-def dev_weight(c):
-    """the case's weights on the device: 16-byte aligned, or -- misaligned -- a contiguous view one float off"""
-    R, D = c["w"].shape
-    if c.get("misaligned"):
-        buf = torch.zeros(R * D + 1, device=DEV)
-        w = buf[1:].view(R, D)
-        assert w.data_ptr() % 16 == 4 and w.is_contiguous()
-    else:
-        w = torch.empty((R, D), device=DEV)
-        assert w.data_ptr() % 16 == 0
-    w.copy_(torch.from_numpy(c["w"]))
-    return w
-
-
-def batch(c, mode):
-    psw = torch.from_numpy(c["psw"]).to(DEV) if mode == "sum" else None
-    return torch.from_numpy(c["idx"]).to(DEV), torch.from_numpy(c["off"]).to(DEV), psw
-
-
-def report(what, got, ref, u, f):
-    print(f"[dense-tables] {what}: kernel {R64.default_units(got, ref):.3f}, plain fp32 {u:.3f} default bounds from float64 "
-          f"-> bound x{f:.2f}")
-
-
-def grad_bound(G, f):
-    g = np.abs(G)
-    return f * (ATOL_SCALE * max(float(g.max()) if g.size else 0.0, 1e-30) + RTOL * g)
-
-
-def own_bound(w):
-    return RTOL * np.abs(w) + 2e-7 * max(float(np.abs(w).max()) if w.size else 0.0, 1e-30)
-
-
-def assert_within(got, ref, tol, what):
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    assert np.isfinite(err).all(), what
-    if (err > tol).any():
-        i = np.unravel_index(np.argmax(err - tol), err.shape)
-        raise AssertionError(f"{what}: {int((err > tol).sum())}/{err.size} out of tolerance; worst at {i}: got {got[i]!r} ref {ref[i]!r} "
-                             f"tol {tol[i]:.3e}")
-
-
-def rowwise_bound(w_ref, s_ref, G, f, lr, eps):
-    """w = w0 - lr G / (sqrt(s) + eps), s = s0 + mean_e G_e^2, with G within dG: |dw| <= lr dG / den + lr |G| ds / (2 sqrt(s) den^2),
-    ds <= mean_e(2 |G_e| dG_e + dG_e^2) plus two fp32 ulps of s; and the fp32 rounding of w itself"""
-    dG = grad_bound(G, f)
-    ds = (2 * np.abs(G) * dG + dG * dG).mean(axis=1) + 2 * np.spacing(s_ref.astype(np.float32)).astype(np.float64)
-    den = np.sqrt(s_ref) + eps
-    dw = lr * dG / den[:, None] + lr * np.abs(G) * (ds / (2 * np.sqrt(s_ref) * den * den))[:, None]
-    return own_bound(w_ref) + dw, ds
 
 
 @pytest.mark.parametrize("mode", ["sum", "mean", "max"])
 @pytest.mark.parametrize("name", CASES)
 def test_kernels_against_float64(name, mode):
-    E = eng()
-    c, ref = case(name), reference(name, mode)
-    idx, off, psw = batch(c, mode)
-    base, pads = c["base"].tolist(), c["pads"]
-    w0 = dev_weight(c)
-    d_out = torch.from_numpy(c["d_out"]).to(DEV)
-    touched = ref["touched"]
-    # ---- forward
-    out, live, arg = E.dense_bags_forward(idx, off, base, w0, mode, pads, psw)
-    got = out.cpu().numpy()
-    if mode == "max":
-        assert np.array_equal(got, ref["out"].astype(np.float32)), "max: the output is a selection -- exact"
-        assert np.array_equal(arg.cpu().numpy(), ref["arg"]), "max: argmax"
-    else:
-        f, u = R64.widen_factor(ref["out32"], ref["out"])
-        report(f"{name} {mode} forward", got, ref["out"], u, f)
-        assert_close(got, ref["out"], f"{name} {mode} forward", rtol=RTOL * f, atol_scale=ATOL_SCALE * f)
-    if mode == "mean":
-        assert np.array_equal(live.cpu().numpy(), ref["live"])
-    empty = ref["live"] == 0
-    assert not got[empty].any(), "a bag without a live slot is exact zeros"
-    out2, live2, arg2 = E.dense_bags_forward(idx, off, base, w0, mode, pads, psw)
-    assert torch.equal(out, out2) and (arg is None or torch.equal(arg, arg2)), "forward: bit-identical from run to run"
-    # ---- the dense gradient
-    f, u = R64.widen_factor(ref["G32"], ref["G"])
-
-    def run(optim, state=None, want=False):
-        w = dev_weight(c)
-        s = None if state is None else torch.from_numpy(state).to(DEV)
-        d_w, d_psw = E.dense_bags_backward(optim, idx, off, base, w, d_out, mode, pads, psw, live, arg, LR, EPS, s, want)
-        return w, s, d_w, d_psw
-
-    _, _, d_w, d_psw = run(E.OPTIM_DENSE, want=mode == "sum")
-    gw = d_w.cpu().numpy()
-    report(f"{name} {mode} G", gw, ref["G"], u, f)
-    assert_close(gw, ref["G"], f"{name} {mode} dense gradient", rtol=RTOL * f, atol_scale=ATOL_SCALE * f)
-    assert not gw[~touched].any(), "dense: rows the batch does not touch are exactly zero"
-    assert torch.equal(d_w, run(E.OPTIM_DENSE)[2]), "dense gradient: bit-identical from run to run"
-    # ---- fused SGD, and the weights' gradient from the pre-update weights
-    w, _, _, d_psw_f = run(E.OPTIM_SGD, want=mode == "sum")
-    gw = w.cpu().numpy()
-    want_w = DR.sgd(c["w"], ref["G"], touched, LR)
-    assert_within(gw, want_w, own_bound(want_w) + LR * grad_bound(ref["G"], f), f"{name} {mode} sgd weights")
-    assert np.array_equal(gw[~touched], c["w"][~touched]), "sgd: untouched rows keep their weights bit for bit"
-    assert torch.equal(w, run(E.OPTIM_SGD)[0]), "sgd: bit-identical from run to run"
-    if mode == "sum":
-        fp, up = R64.widen_factor(ref["d_psw32"], ref["d_psw"])
-        report(f"{name} d_psw", d_psw_f.cpu().numpy(), ref["d_psw"], up, fp)
-        assert_close(d_psw_f.cpu().numpy(), ref["d_psw"], f"{name} d_psw under fused sgd", rtol=RTOL * fp, atol_scale=ATOL_SCALE * fp)
-        assert torch.equal(d_psw_f, d_psw), "d_psw: the same from the dense route (the weights before the update)"
-        _, row = DR.lookups(c["idx"], c["off"], c["base"], c["B"], pads)
-        assert not d_psw_f.cpu().numpy()[row < 0].any(), "d_psw is 0 at padding"
-    # ---- element-wise Adagrad from a live, all-distinct state
-    w, s, _, _ = run(E.OPTIM_ADAGRAD, c["s_elem"])
-    want_w, want_s = DR.adagrad(c["w"], c["s_elem"], ref["G"], touched, LR, EPS)
-    gw, gs = w.cpu().numpy(), s.cpu().numpy()
-    R64.assert_state_close(gs, want_s, ref["G"], f"{name} {mode} adagrad state", scale=f)
-    assert_adagrad_close(gw, want_w, ref["G"], f"{name} {mode} adagrad weights", lr=LR, eps=EPS, state0=c["s_elem"], scale=f)
-    assert np.array_equal(gw[~touched], c["w"][~touched]) and np.array_equal(gs[~touched], c["s_elem"][~touched]), \
-        "adagrad: untouched rows keep weights and state bit for bit"
-    w2, s2, _, _ = run(E.OPTIM_ADAGRAD, c["s_elem"])
-    assert torch.equal(w, w2) and torch.equal(s, s2), "adagrad: bit-identical from run to run"
-    # ---- row-wise Adagrad
-    w, s, _, _ = run(E.OPTIM_ADAGRAD, c["s_row"])
-    want_w, want_s = DR.rowwise_adagrad(c["w"], c["s_row"], ref["G"], touched, LR, EPS)
-    gw, gs = w.cpu().numpy(), s.cpu().numpy()
-    tol_w, tol_s = rowwise_bound(want_w, want_s, ref["G"], f, LR, EPS)
-    assert_within(gs, want_s, tol_s, f"{name} {mode} row-wise state")
-    assert_within(gw, want_w, tol_w, f"{name} {mode} row-wise weights")
-    assert np.array_equal(gw[~touched], c["w"][~touched]) and np.array_equal(gs[~touched], c["s_row"][~touched])
-    w2, s2, _, _ = run(E.OPTIM_ADAGRAD, c["s_row"])
-    assert torch.equal(w, w2) and torch.equal(s, s2), "row-wise adagrad: bit-identical from run to run"
+    check_kernels(name, mode, case(name), reference(name, mode))
 
 
 def test_cases_reach_what_they_are_for():
