@@ -18,7 +18,9 @@ the batch share one contraction),
 `bag_max_pool`, `bag_max_pool_backward` and `tt_backward_rows`, padded bags' `bags_compact`, the unpooled lookup's `rows_expand` /
 `rows_collect` (and, with a live cache, `preprocess_indices_async`, `rows_place` / `rows_pick`), `bags_merge` (the per-table
 batches of a mixed-cardinality group -> one table-major batch, one launch), and the row cache over several tables' `table_keys`,
-`table_keys_split` and `cache_populate_tables`, and `cache_carry` (trained cache rows and their state across a re-populate).
+`table_keys_split` and `cache_populate_tables`, `cache_carry` (trained cache rows and their state across a re-populate), the
+dense member tables' `dense_bags_forward` / `dense_bags_backward`, and `adam_apply` (one fused Adam / AdamW step over a list of
+dense tensors: OptimType.EXACT_ADAM).
 """
 import ctypes as C
 import os
@@ -207,6 +209,10 @@ def _load(path):
     L.ttx_dense_bags_backward.argtypes = [i32, i32, i64, i32, i64, vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, i32, vp, vp, vp,
                                           vp, vp, sz, vp]
     L.ttx_dense_bags_info.argtypes = [i32, i64, C.POINTER(i32)]
+    # fused Adam over a list of dense tensors
+    L.ttx_adam_apply_workspace_bytes.restype = C.c_size_t
+    L.ttx_adam_apply_workspace_bytes.argtypes = [i32]
+    L.ttx_adam_apply.argtypes = [i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, i32, vp, sz, vp]
     return L
 
 
@@ -1473,6 +1479,45 @@ def dense_bags_info(D: int, nnz: int) -> dict:
     out = (C.c_int32 * 2)()
     _check(lib().ttx_dense_bags_info(int(D), int(nnz), out))
     return {"split": int(out[0]), "one_launch": int(out[1])}
+
+
+# ---- fused Adam over a list of dense tensors (include/ttx.h "fused Adam"; csrc/ttx_adam.hip) ----
+ADAM_MAX_TENSORS = 16
+
+
+def adam_apply(weights: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avg: Sequence[torch.Tensor],
+               exp_avg_sq: Sequence[torch.Tensor], step: torch.Tensor, lr: float, betas: Tuple[float, float], eps: float,
+               weight_decay: float = 0.0, decoupled: bool = False) -> None:
+    """One torch.optim.Adam (decoupled: AdamW) step, in place, on up to 16 float32 GPU tensors: `weights[k]`, `exp_avg[k]` and
+    `exp_avg_sq[k]` are updated from `grads[k]` (same number of elements, each dense in memory -- a view offset into a buffer is
+    fine), `step` (int64 [1] on the device: steps taken so far) is advanced by one.  Nothing is read back: capturable.  With no
+    tensor, or elements, nothing is launched and `step` stays."""
+    n = len(weights)
+    if not (len(grads) == len(exp_avg) == len(exp_avg_sq) == n):
+        raise RuntimeError("tt_embeddings: adam_apply: weights, grads, exp_avg and exp_avg_sq must have one entry per tensor")
+    if n > ADAM_MAX_TENSORS:
+        raise RuntimeError(f"tt_embeddings: adam_apply: at most {ADAM_MAX_TENSORS} tensors per call, got {n}")
+    dev = _dev(step)
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise RuntimeError("tt_embeddings: adam_apply: step must be one int64 on the device")
+    keep = []
+    for k in range(n):
+        w = weights[k].detach() if weights[k].requires_grad else weights[k]
+        four = (w, grads[k], exp_avg[k], exp_avg_sq[k])
+        for name, t in zip(("weights", "grads", "exp_avg", "exp_avg_sq"), four):
+            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != dev or t.numel() != w.numel():
+                raise RuntimeError(f"tt_embeddings: adam_apply: {name}[{k}] must be a contiguous float32 tensor on {dev} of "
+                                   f"{w.numel()} elements, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        keep.append(four)
+    numel = (C.c_int64 * max(n, 1))(*[f[0].numel() for f in keep])
+    ptrs = [_ptr_array([f[j] for f in keep]) for j in range(4)]
+    lb = lib()
+    st = _stream(dev)
+    ws = _workspace(dev, st, lb.ttx_adam_apply_workspace_bytes(n))
+    with _guard(dev):
+        _check(lb.ttx_adam_apply(n, numel, ptrs[0], ptrs[1], ptrs[2], ptrs[3], step.data_ptr(), float(lr), float(betas[0]),
+                                 float(betas[1]), float(eps), float(weight_decay), 1 if decoupled else 0, ws.data_ptr(), ws.numel(),
+                                 st))
 
 
 def profile_enable(mask: int) -> None:

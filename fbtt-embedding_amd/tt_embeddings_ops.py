@@ -165,6 +165,7 @@ class OptimType(Enum):
     LARS_SGD = "lars_sgd"
     PARTIAL_ROWWISE_ADAM = "partial_row_wise_adam"
     PARTIAL_ROWWISE_LAMB = "partial_row_wise_lamb"
+    EXACT_ADAM = "exact_adam"  # (not in the reference: torch.optim.Adam / AdamW on the cores, fused -- DESIGN.md 4.17)
 
     def __str__(self) -> str:
         return self.value
@@ -363,6 +364,71 @@ def _grad_tuple(node, n_cores: int, core_grads=None, d_cache_weight: Optional[to
     if d_cache_weight is not None:
         head[node.CACHE_WEIGHT_ARG] = d_cache_weight
     return tuple(head + (list(core_grads) if core_grads is not None else [None] * n_cores))
+
+
+# --------------------------------------------------------------------------- #
+# OptimType.EXACT_ADAM (not in the reference): torch.optim.Adam / AdamW on the cores, applied in backward
+# --------------------------------------------------------------------------- #
+# TT cores have no sparsity a lazy optimizer could use, so the semantics are torch.optim.Adam's: every element of every core
+# steps at every backward.  The module runs every one of its lookup routes exactly as it runs them for sparse=False (dense core
+# gradients: `_route_args`), with the cores passed through `_AdamStepFunction` first: forward hands the cores on as they are,
+# backward receives all core gradients in ONE call, applies the step (`_engine.adam_apply`: two launches for all cores) and
+# returns no gradient -- the cores' .grad stays None, as under the other fused optimizers.  No lookup node, kernel or route
+# choice knows about it.
+
+def _check_adam_args(betas, weight_decay: float) -> Tuple[float, float, float]:
+    b1, b2 = (float(b) for b in betas)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"betas must lie in [0, 1), got {tuple(betas)!r}")
+    if not float(weight_decay) >= 0.0:
+        raise ValueError(f"weight_decay must not be negative, got {weight_decay!r}")
+    return b1, b2, float(weight_decay)
+
+
+def _adam_apply_torch(weights, grads, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay=0.0, decoupled=False) -> None:
+    """`_engine.adam_apply`'s formula with torch ops: what the step runs on CPU tensors (the tests' oracle engine has no
+    adam_apply).  Reads the step back: not for GPU tensors."""
+    b1, b2 = betas
+    t = int(step.item()) + 1
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    with torch.no_grad():
+        for w, g, m, v in zip(weights, grads, exp_avg, exp_avg_sq):
+            g = g.reshape(w.shape)
+            if weight_decay != 0.0:
+                if decoupled:
+                    w.mul_(1.0 - lr * weight_decay)
+                else:
+                    g = g.add(w, alpha=weight_decay)
+            m.mul_(b1).add_(g, alpha=1.0 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+            w.addcdiv_(m, v.sqrt().mul_(1.0 / math.sqrt(bc2)).add_(eps), value=-lr / bc1)
+        step.add_(1)
+
+
+def _adam_step(weights, grads, exp_avg, exp_avg_sq, step, lr, eps, adam) -> None:
+    """one Adam step on `weights` (detached Parameters) in place; `adam` = (beta1, beta2, weight_decay, decoupled)"""
+    grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
+    fn = getattr(_engine, "adam_apply", None)
+    if fn is None or not weights[0].is_cuda:
+        fn = _adam_apply_torch
+    fn(weights, grads, exp_avg, exp_avg_sq, step, float(lr), (adam[0], adam[1]), float(eps), adam[2], adam[3])
+
+
+class _AdamStepFunction(torch.autograd.Function):
+    """The cores (or a dense group's weight) on their way into a lookup under OptimType.EXACT_ADAM.  forward: the tensors as they
+    are.  backward: ONE Adam step of `module` from all their gradients (`module._adam_step_from`), no gradient handed on.
+    `live` False (an empty batch): no step."""
+
+    @staticmethod
+    def forward(ctx, module, live: bool, *tensors: torch.Tensor):
+        ctx.module, ctx.live = module, live
+        return tuple(t.view_as(t) for t in tensors)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if ctx.live:
+            ctx.module._adam_step_from(grads)
+        return (None, None) + (None,) * len(grads)
 
 
 class TTLookupFunction(torch.autograd.Function):
@@ -727,8 +793,12 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
                  reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
-                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
+                 mode: str = "sum", padding_idx: Optional[int] = None, betas: Tuple[float, float] = (0.9, 0.999),
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False) -> None:
         super().__init__()
+        # betas, weight_decay, decoupled_weight_decay (trailing keywords, not in the reference): read under
+        # optimizer=OptimType.EXACT_ADAM only -- torch.optim.Adam's (decoupled_weight_decay=True: AdamW's) step on all cores inside
+        # backward, `learning_rate` and `eps` being the existing arguments (`_init_adam`)
         # mode (trailing keyword, not in the reference): nn.EmbeddingBag's pooling -- "sum" (the reference's, the default here),
         # "mean" (the bag sum over the bag length: a per-bag scale around the sum lookup, every route) or "max" (column-wise max,
         # the gradient to the winning lookup only: rows, max pool and a per-lookup backward; no live cache, no dedup, no n_dev)
@@ -816,11 +886,12 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         self.register_buffer("L", torch.tensor(strides, dtype=torch.int64, device=device))
         self.tt_cores = nn.ParameterList()
         self.optimizer_state = BufferList("optimizer_state")
-        stateful = optimizer not in _SGD_LIKE
+        stateful = optimizer not in _SGD_LIKE and (sparse or optimizer != OptimType.EXACT_ADAM)  # (Adam's state: with sparse=True only)
         for t in range(nd):
             shape = (num_tables, self.tt_p_shapes[t], self.tt_ranks[t] * self.tt_q_shapes[t] * self.tt_ranks[t + 1])
             self.tt_cores.append(nn.Parameter(torch.empty(shape, device=device, dtype=torch.float32)))
             self.optimizer_state.append(torch.zeros(shape if stateful else 0, device=device, dtype=torch.float32))
+        self._init_adam(betas, weight_decay, decoupled_weight_decay, use_cache)
         self.reset_parameters(weight_dist)
         self.use_cache = use_cache
         if use_cache:
@@ -852,6 +923,34 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             self.cache_optimizer_state = None
             self.cache_weight = None
         self.warmup = True
+
+    # ------------------------------------------------------- OptimType.EXACT_ADAM
+    def _init_adam(self, betas, weight_decay: float, decoupled: bool, use_cache: bool) -> None:
+        """called by the constructors once tt_cores / optimizer_state exist.  Under sparse=True and OptimType.EXACT_ADAM:
+        `optimizer_state{t}` is exp_avg, the second BufferList `optimizer_state_v` exp_avg_sq (both in the core's shape) and the
+        buffer `optimizer_step` int64 [1] the steps taken.  Every other module gets no new buffer: its state_dict() is unchanged."""
+        self._adam = None
+        if not (self.sparse and self.optimizer == OptimType.EXACT_ADAM):
+            return
+        if use_cache:
+            # (cached rows would need per-row moments that move with the rows in cache_populate(keep_trained=): a piece of its own)
+            raise NotImplementedError("OptimType.EXACT_ADAM does not support use_cache=True (the cache rows have no Adam state)")
+        b1, b2, wd = _check_adam_args(betas, weight_decay)
+        self._adam = (b1, b2, wd, bool(decoupled))
+        self.optimizer_state_v = BufferList("optimizer_state_v", [torch.zeros_like(s) for s in self.optimizer_state])
+        self.register_buffer("optimizer_step", torch.zeros(1, dtype=torch.int64, device=self.tt_cores[0].device))
+
+    def _route_args(self, live: bool = True):
+        """-> (sparse, cores) as the lookup routes see them.  Under OptimType.EXACT_ADAM: (False, the cores passed through
+        _AdamStepFunction) -- every route runs as for sparse=False, and the dense core gradients end in ONE Adam step per backward.
+        `live` False: the batch is empty, backward takes no step."""
+        if self.__dict__.get("_adam") is None:
+            return self.sparse, self.tt_cores
+        return False, list(_AdamStepFunction.apply(self, live, *self.tt_cores))
+
+    def _adam_step_from(self, grads) -> None:
+        _adam_step([p.detach() for p in self.tt_cores], grads, list(self.optimizer_state), list(self.optimizer_state_v),
+                   self.optimizer_step, self.learning_rate, self.eps, self._adam)
 
     # ------------------------------------------------------------------ init
     def full_weight(self) -> torch.Tensor:
@@ -1276,17 +1375,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     def _forward_split0(self, fast, indices: torch.Tensor, offsets: torch.Tensor, k: int) -> torch.Tensor:
         """q0 = k q0': k part lookups per index through the C++ node on the table [k p0, p1, p2] x [q0', q1, q2] (views of
         core 0 and its optimizer state: the same memory); the output [tables, k B, D / k] IS [tables, B, D]."""
-        use_state, optim = _optim_code(self.sparse, self.optimizer)
+        sparse, tt_cores = self._route_args()
+        use_state, optim = _optim_code(sparse, self.optimizer)
         if self.use_cache and self.num_tables == 1:  # (the frequency table counts the caller's indices, not the part lookups;
             _engine.update_cache_state(indices, self.hashtbl, self.cache_freq)  # several tables: _forward_sum counted their keys)
         p, q, nt = self.tt_p_shapes, self.tt_q_shapes, self.num_tables
         vi, vo = _engine.split0_expand(indices, offsets, k, p[1] * p[2])
         Q = self.__dict__.get("_pad0", 0) or q[0]
-        c0 = self.tt_cores[0]
+        c0 = tt_cores[0]
         s0 = self.optimizer_state[0] if use_state else None
         if Q != q[0]:  # core 0 (and its optimizer state) zero-padded to Q slots: `_pad0_target`
-            c0, s0 = self._padded0(Q, optim, use_state)
-        cores = [c0.view(nt, k * p[0], c0.size(2) // k), self.tt_cores[1], self.tt_cores[2]]
+            c0, s0 = self._padded0(Q, optim, use_state, c0)
+        cores = [c0.view(nt, k * p[0], c0.size(2) // k), tt_cores[1], tt_cores[2]]
         state = [s0.view(nt, k * p[0], s0.size(2) // k), self.optimizer_state[1], self.optimizer_state[2]] if use_state else []
         out = fast.lookup(vi, vo, nt, [k * p[0], p[1], p[2]], [Q // k, q[1], q[2]], self.tt_ranks, optim,
                           self.learning_rate, self.eps, None, None, state, cores, None, None, None, None)
@@ -1300,7 +1400,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         # (a copy, not the strided prefix view: callers of the reference's module get a contiguous [tables, B, D])
         return out.view(nt, B, Q * q[1] * q[2])[:, :, :self.embedding_dim].contiguous()
 
-    def _padded0(self, Q: int, optim: int, use_state: bool):
+    def _padded0(self, Q: int, optim: int, use_state: bool, c0: Optional[torch.Tensor] = None):
         """core 0 [tables, p0, q0 r1] zero-padded to [tables, p0, Q r1] (and the same of its optimizer state).  Dense gradients
         (sparse=False): an autograd pad of the Parameter, every step.  Fused optimizers: a buffer the module keeps, refreshed from
         the Parameter (and the optimizer state) EVERY step -- p0 q0 r1 floats, one small copy.  (Round 4 refreshed only when the
@@ -1308,8 +1408,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         move the version, the next step then trained the stale copy and the write-back hook overwrote the caller's update: round 4
         advisor.)"""
         c, w = self.tt_cores[0], (Q - self.tt_q_shapes[0]) * self.tt_ranks[1]
-        if optim == 2:
-            return torch.nn.functional.pad(c, (0, w)), None
+        if optim == 2:  # (c0: core 0 as the route sees it -- `_route_args`)
+            return torch.nn.functional.pad(c if c0 is None else c0, (0, w)), None
         sh = self.__dict__.get("_sh0")
         if sh is None or sh[0].device != c.device:
             mk = lambda: torch.zeros(c.size(0), c.size(1), c.size(2) + w, device=c.device, dtype=c.dtype)  # noqa: E731
@@ -1349,13 +1449,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         offsets = offsets.long() if offsets.dtype != torch.int64 else offsets
         indices = indices if indices.is_contiguous() else indices.contiguous()
         offsets = offsets if offsets.is_contiguous() else offsets.contiguous()
-        use_state, optim = _optim_code(self.sparse, self.optimizer)
+        sparse, tt_cores = self._route_args()
+        use_state, optim = _optim_code(sparse, self.optimizer)
         p_flat = getattr(self, "_p_flat", self.tt_p_shapes)
         pre = fast.prologue(indices, offsets, self.num_tables, p_flat, self.tt_q_shapes, self.tt_ranks, None, None,
                             n_dev.to(torch.int32).reshape(1))
         return fast.lookup(indices, offsets, self.num_tables, p_flat, self.tt_q_shapes, self.tt_ranks, optim,
                            self.learning_rate, self.eps, None, None, list(self.optimizer_state) if use_state else [],
-                           list(self.tt_cores), None, *pre)
+                           list(tt_cores), None, *pre)
 
     def _det_bits(self) -> int:
         """the C++ node's encoding of deterministic_cache_update (csrc/ttx_torch.cpp: bit 9 sorted, bit 10 atomics, neither auto)"""
@@ -1494,10 +1595,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             # (q0 > 4: the unsplit geometry on the generic kernels -- the part lookups of the sum route would split a bag's
             #  columns over k part bags, each with its own winner per column, which is the same max, but their gradient rows
             #  would need the part layout: not worth a route of its own)
+            sparse, tt_cores = self._route_args(indices.numel() > 0)
             return TTMaxLookupFunction.apply(
                 (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks,
-                indices.contiguous(), offsets.contiguous(), self.optimizer, self.learning_rate, self.eps, self.sparse,
-                list(self.optimizer_state), *self.tt_cores)
+                indices.contiguous(), offsets.contiguous(), self.optimizer, self.learning_rate, self.eps, sparse,
+                list(self.optimizer_state), *tt_cores)
         # mean: the bag lengths come from the offsets in their closing-entry form (n_dev: the caller's, which must have it)
         bag_offsets = offsets.long() if n_dev is not None else self._normalise(indices, offsets, closed)[1]
         summed = self._forward_sum(indices, offsets, warmup, None, n_dev, closed)
@@ -1589,19 +1691,21 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 frac = float(dd[:4].view(torch.int32).item()) / max(n_tt, 1) if dd is not None else 1.0
                 self._dd_auto = [frac <= _DEDUP_AUTO_MAX_DISTINCT, _DEDUP_AUTO_PERIOD]
                 self._dd_auto_last = frac
+            sparse, tt_cores = self._route_args()
             return TTLookupFunction.apply(
                 (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes,
                 self.tt_ranks, self.L, n_tt, 0, indices, rowidx, tableidx, self.optimizer, self.learning_rate,
-                self.eps, self.sparse, None, self.cache_optimizer_state, self.cache_weight,
-                list(self.optimizer_state), *self.tt_cores)
+                self.eps, sparse, None, self.cache_optimizer_state, self.cache_weight,
+                list(self.optimizer_state), *tt_cores)
         if (self.__dict__.get("_split0", 0) > 1 and fast is not None and self.warmup and indices.is_cuda and indices.numel() > 0
                 and per_sample_weights is None and not hasattr(self, "_p_flat")):
             return self._forward_split0(fast, indices, offsets, self._split0)
         if fast is not None and self.warmup and indices.is_cuda and indices.numel() > 0:
             # cache not live: the whole lookup (prologue, forward, and the backward / fused optimizer node)
             # is the C++ autograd node of csrc/ttx_torch.cpp -- same C ABI calls, no interpreter in between
-            use_state = self.sparse and self.optimizer not in _SGD_LIKE
-            optim = 2 if not self.sparse else (1 if use_state else 0)
+            adam = d.get("_adam") is not None  # (EXACT_ADAM: dense gradients of the cores as `_route_args` hands them on)
+            use_state = self.sparse and self.optimizer not in _SGD_LIKE and not adam
+            optim = 2 if not self.sparse or adam else (1 if use_state else 0)
             pre = self._take_prefetched(indices, offsets)  # (rowidx, tableidx, plan) if prefetch() ran for this batch
             count = self.use_cache and not self._pf_counted
             fa = self.__dict__.get("_fa")  # (cores, state, hashtbl, cache_freq, p): looked up once, not per step -- every
@@ -1611,6 +1715,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                 fa = self._fa = (list(self.tt_cores), list(self.optimizer_state), self.hashtbl if self.use_cache else None,
                                  self.cache_freq if self.use_cache else None,
                                  getattr(self, "_p_flat", self.tt_p_shapes))  # (per-table factors: flattened)
+            if adam:  # (this step's aliases of the cores, in the place of the Parameters)
+                fa = (self._route_args()[1],) + fa[1:]
             out = fast.lookup(indices if indices.is_contiguous() else indices.contiguous(),
                               offsets if offsets.is_contiguous() else offsets.contiguous(), self.num_tables, fa[4],
                               self.tt_q_shapes, self.tt_ranks, optim, self.learning_rate, self.eps,
@@ -1668,13 +1774,16 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         det = self.__dict__.get("deterministic_cache_update")
         if det is not None and n_cached > 0:
             rowidx._ttx_det = bool(det)  # (picked up by TTLookupFunction.forward, like the plan: the reference's 19 arguments stay)
+        sparse, tt_cores = self._route_args(indices.numel() > 0)
         return TTLookupFunction.apply(
             (offsets.numel() - 1) // self.num_tables, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes,
             self.tt_ranks, self.L, n_tt, n_cached, indices, rowidx, tableidx, self.optimizer, self.learning_rate,
-            self.eps, self.sparse, cache_locations, self.cache_optimizer_state, self.cache_weight,
-            list(self.optimizer_state), *self.tt_cores)
+            self.eps, sparse, cache_locations, self.cache_optimizer_state, self.cache_weight,
+            list(self.optimizer_state), *tt_cores)
 
     def set_learning_rate(self, lr: float) -> None:
+        """takes effect on the next step (every fused optimizer, OptimType.EXACT_ADAM included; eager steps between graph captures
+        too).  A step captured in a hipGraph has its learning rate baked in: capture again after changing it."""
         self.learning_rate = lr
 
     def get_params(self) -> List[torch.Tensor]:
@@ -1694,11 +1803,12 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, include_last_offset: bool = True, dedup: bool = False,
                  reference_exact_populate: bool = False, deterministic_cache_update: Optional[bool] = None,
-                 mode: str = "sum", padding_idx: Optional[int] = None) -> None:
+                 mode: str = "sum", padding_idx: Optional[int] = None, betas: Tuple[float, float] = (0.9, 0.999),
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
                          enforce_embedding_dim, device, include_last_offset, dedup, reference_exact_populate,
-                         deterministic_cache_update, mode, padding_idx)
+                         deterministic_cache_update, mode, padding_idx, betas, weight_decay, decoupled_weight_decay)
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1746,12 +1856,14 @@ class TTEmbedding(TTEmbeddingBag):
                  sparse: bool = True, weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  device: Optional[torch.device] = None, padding_idx: Optional[int] = None, dedup: bool = False,
                  use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0, reference_exact_populate: bool = False,
-                 deterministic_cache_update: Optional[bool] = None) -> None:
+                 deterministic_cache_update: Optional[bool] = None, betas: Tuple[float, float] = (0.9, 0.999),
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False) -> None:
         super().__init__(num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer, learning_rate, eps,
                          sparse, use_cache=bool(use_cache), cache_size=cache_size, hashtbl_size=hashtbl_size, weight_dist=weight_dist,
                          enforce_embedding_dim=enforce_embedding_dim, device=device, include_last_offset=True, dedup=bool(dedup),
                          reference_exact_populate=reference_exact_populate, deterministic_cache_update=deterministic_cache_update,
-                         mode="sum", padding_idx=padding_idx)
+                         mode="sum", padding_idx=padding_idx, betas=betas, weight_decay=weight_decay,
+                         decoupled_weight_decay=decoupled_weight_decay)
 
     def prefetch(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> bool:
         return False  # (no prologue to plan ahead: there are no bags)
@@ -1764,14 +1876,14 @@ class TTEmbedding(TTEmbeddingBag):
         n = live.numel()
         return self._forward_sum(live, self._fixed_offsets(live.device, n, 1), closed=True).view(n, self.embedding_dim)
 
-    def _split_geometry(self, use_state: bool):
+    def _split_geometry(self, use_state: bool, tt_cores=None):
         """-> (k, p, q, cores, state): the geometry a rows lookup runs on.  q0 = k q0' with an exact split: k part lookups per
         position in the table [k p0, p1, p2] x [q0', q1, q2] (views of core 0 and its optimizer state: the same memory); k = 1
         otherwise (the module's own geometry)."""
         k = self.__dict__.get("_split0", 0) if not self.__dict__.get("_pad0", 0) else 0
         k = k if k > 1 else 1
         p, q = self.tt_p_shapes, self.tt_q_shapes
-        cores, state = list(self.tt_cores), list(self.optimizer_state) if use_state else []
+        cores, state = list(self.tt_cores if tt_cores is None else tt_cores), list(self.optimizer_state) if use_state else []
         if k > 1:
             c0 = cores[0]
             cores[0] = c0.view(1, k * p[0], c0.size(2) // k)
@@ -1783,9 +1895,10 @@ class TTEmbedding(TTEmbeddingBag):
     def _no_live_rows(self, flat: torch.Tensor, N: int) -> torch.Tensor:
         """no live lookup (an empty batch, or N positions of padding only) -> [N, D] zeros through the empty lookup's node, whose
         backward trains nothing and gives zero dense gradients"""
+        sparse, tt_cores = self._route_args(False)
         out = TTRowsLookupFunction.apply(0, self.embedding_dim, 1, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat[:0], None,
-                                         None, self.optimizer, self.learning_rate, self.eps, self.sparse,
-                                         list(self.optimizer_state), *self.tt_cores)
+                                         None, self.optimizer, self.learning_rate, self.eps, sparse,
+                                         list(self.optimizer_state), *tt_cores)
         return out if N == 0 else torch.zeros((N, self.embedding_dim), dtype=torch.float32, device=flat.device) + out.sum()
 
     def _forward_cached(self, flat: torch.Tensor, N: int, pad: Optional[int], use_state: bool) -> torch.Tensor:
@@ -1818,7 +1931,7 @@ class TTEmbedding(TTEmbeddingBag):
         flat = flat if flat.is_contiguous() else flat.contiguous()
         N = flat.numel()
         pad = self.__dict__.get("padding_idx")
-        use_state, _ = _optim_code(self.sparse, self.optimizer)
+        use_state, _ = _optim_code(self.sparse and self.__dict__.get("_adam") is None, self.optimizer)
         if N == 0:
             return self._no_live_rows(flat, 0).view(shape + (D,))
         if not flat.is_cuda:
@@ -1828,8 +1941,8 @@ class TTEmbedding(TTEmbeddingBag):
                 return self._bag_rows(flat).view(shape + (D,))
             keep = torch.nonzero(flat != pad).flatten()
             out = torch.zeros((N, D), dtype=torch.float32, device=flat.device)
-            if keep.numel() == 0:
-                out = out + sum(c.sum() for c in self.tt_cores) * 0.0  # (zero dense gradients, as an empty batch gives)
+            if keep.numel() == 0:  # (zero dense gradients, as an empty batch gives; EXACT_ADAM: no step)
+                out = out + sum(c.sum() for c in self._route_args(False)[1]) * 0.0
             else:
                 out = out.index_put((keep,), self._bag_rows(flat[keep].contiguous()))
             return out.view(shape + (D,))
@@ -1862,7 +1975,8 @@ class TTEmbedding(TTEmbeddingBag):
                     raise RuntimeError("TTEmbedding(use_cache=True, padding_idx=): the live count is read back to the host to count "
                                        "the live indices -- not capturable in a hipGraph on this route")
                 self.update_cache(flat[:int(n_dev.item())])
-        k, p, q, cores, state = self._split_geometry(use_state)
+        sparse, tt_cores = self._route_args()
+        k, p, q, cores, state = self._split_geometry(use_state, tt_cores)
         if k > 1:
             # position n's parts are lookups k n .. k n + k - 1, their rows of D / k columns ARE row n of [N, D]; of a compacted
             # batch the first k n_live part lookups are the live ones
@@ -1870,5 +1984,5 @@ class TTEmbedding(TTEmbeddingBag):
             if n_dev is not None:
                 n_dev = n_dev * k
         out = TTRowsLookupFunction.apply(N, D, k, p, q, self.tt_ranks, flat, rank, n_dev, self.optimizer, self.learning_rate, self.eps,
-                                         self.sparse, state, *cores)
+                                         sparse, state, *cores)
         return out.view(shape + (D,))

@@ -7,7 +7,7 @@ row once, without atomics (`ttx_dense_bags_backward`: fused SGD / Adagrad, or th
 of `TableBatchedTTEmbeddingBag` and returns [num_tables, B, D]; `MixedTTEmbeddingBag(dense_below=)` builds it for its small tables.
 GPU tensors only; no cache, no dedup, no prefetch.
 """
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -55,7 +55,9 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
 
     `num_embeddings`: the tables' cardinalities (at most 64).  `optimizer` / `learning_rate` / `eps` / `sparse`: as on the TT
     modules -- sparse=True applies the fused update in backward (SGD / EXACT_SGD: SGD; EXACT_ROWWISE_ADAGRAD: one state value
-    per row; every other OptimType: element-wise Adagrad, as for the TT cores), sparse=False leaves `weight.grad`.  `mode`:
+    per row; EXACT_ADAM: torch.optim.Adam's step -- AdamW's with `decoupled_weight_decay` -- on the WHOLE weight per backward, with
+    `betas` / `weight_decay`, state `optimizer_state` (exp_avg) and `optimizer_state_v` (exp_avg_sq) [R, D] and `optimizer_step`,
+    DESIGN.md 4.17; every other OptimType: element-wise Adagrad, as for the TT cores), sparse=False leaves `weight.grad`.  `mode`:
     "sum" / "mean" / "max"; `padding_idx`: None, one value, or one entry per table (torch's rule against the table's own
     cardinality); negative indices in the batch are padding too (the merged batches' sentinel).
     forward(indices, offsets=None, per_sample_weights=None): the table-major batch -- 1-D indices with offsets
@@ -64,7 +66,9 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
 
     def __init__(self, num_embeddings: Sequence[int], embedding_dim: int, optimizer: OptimType = OptimType.SGD,
                  learning_rate: float = 0.1, eps: float = 1.0e-10, sparse: bool = True, device: Optional[torch.device] = None,
-                 include_last_offset: bool = True, mode: str = "sum", padding_idx=None) -> None:
+                 include_last_offset: bool = True, mode: str = "sum", padding_idx=None,
+                 betas: Tuple[float, float] = (0.9, 0.999), weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False) -> None:
         super().__init__()
         Es = [int(e) for e in num_embeddings]
         if not 1 <= len(Es) <= MAX_TABLES or any(e <= 0 for e in Es):
@@ -93,13 +97,19 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
             self.row_base.append(self.row_base[-1] + e)
         R, D = self.row_base[-1], self.embedding_dim
         self.weight = nn.Parameter(torch.empty((R, D), device=device, dtype=torch.float32))
-        if optimizer in _SGD_LIKE:
+        self._adam = None
+        if self.sparse and optimizer == OptimType.EXACT_ADAM:
+            self._adam = _ops._check_adam_args(betas, weight_decay) + (bool(decoupled_weight_decay),)
+        if optimizer in _SGD_LIKE or (optimizer == OptimType.EXACT_ADAM and not self.sparse):
             shape = (0,)
         elif optimizer == OptimType.EXACT_ROWWISE_ADAGRAD:
             shape = (R,)
         else:
             shape = (R, D)
         self.register_buffer("optimizer_state", torch.zeros(shape, device=device, dtype=torch.float32))
+        if self._adam is not None:  # (exp_avg_sq and the steps taken; optimizer_state is exp_avg)
+            self.register_buffer("optimizer_state_v", torch.zeros(shape, device=device, dtype=torch.float32))
+            self.register_buffer("optimizer_step", torch.zeros(1, dtype=torch.int64, device=device))
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -109,6 +119,9 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
                 bound = 1.0 / float(e) ** 0.5
                 self.table_weight(k).uniform_(-bound, bound)
             self.optimizer_state.zero_()
+            if self.__dict__.get("_adam") is not None:
+                self.optimizer_state_v.zero_()
+                self.optimizer_step.zero_()
 
     def table_weight(self, k: int) -> torch.Tensor:
         """table k's rows [E_k, D], a view of `weight` (`table_weight(k).copy_(bag.weight)` imports an nn.EmbeddingBag)"""
@@ -122,6 +135,10 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
 
     def set_learning_rate(self, lr: float) -> None:
         self.learning_rate = float(lr)
+
+    def _adam_step_from(self, grads) -> None:
+        _ops._adam_step([self.weight.detach()], grads, [self.optimizer_state], [self.optimizer_state_v], self.optimizer_step,
+                        self.learning_rate, self.eps, self._adam)
 
     def _offsets_2d(self, nb: int, L: int, device) -> torch.Tensor:
         cached = self.__dict__.get("_off2d")
@@ -156,8 +173,13 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
             raise ValueError(f"the batch must describe num_tables * B bags ({self.num_tables} tables), got {nb}")
         flat = indices.reshape(-1).long()
         pads = self.padding_idx if any(v is not None for v in self.padding_idx) else None
+        weight, sparse = self.weight, self.sparse
+        if self.__dict__.get("_adam") is not None:
+            # EXACT_ADAM: the lookup runs as for sparse=False and its weight gradient ends in one Adam step (tt_embeddings_ops
+            # `_AdamStepFunction`); an empty batch takes none
+            (weight,), sparse = _ops._AdamStepFunction.apply(self, flat.numel() > 0, weight), False
         out = DenseLookupFunction.apply(flat, offsets, per_sample_weights, self.row_base, pads, self.mode, self.optimizer,
-                                        self.learning_rate, self.eps, self.sparse, self.optimizer_state, self.weight)
+                                        self.learning_rate, self.eps, sparse, self.optimizer_state, weight)
         return out.view(self.num_tables, nb // self.num_tables, self.embedding_dim)
 
     def extra_repr(self) -> str:

@@ -68,8 +68,11 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  table_ranks: Optional[Sequence[List[int]]] = None, table_q: Optional[Sequence[List[int]]] = None,
                  mode: str = "sum", padding_idx: Optional[int] = None, use_cache: bool = False, cache_size: int = 0,
                  hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None,
-                 reference_exact_populate: bool = False) -> None:
-        """`use_cache`, `cache_size`, `hashtbl_size`, `deterministic_cache_update`, `reference_exact_populate` (trailing keywords, as
+                 reference_exact_populate: bool = False, betas: Tuple[float, float] = (0.9, 0.999), weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False) -> None:
+        """`betas`, `weight_decay`, `decoupled_weight_decay` (trailing keywords, as on the parent): read under
+        optimizer=OptimType.EXACT_ADAM only -- one fused Adam / AdamW step on all cores per backward; not with use_cache=True.
+        `use_cache`, `cache_size`, `hashtbl_size`, `deterministic_cache_update`, `reference_exact_populate` (trailing keywords, as
         on the parent): ONE LFU row cache over all the tables, keyed by key_base[table] + index with key_base the
         running sum of the tables' prod(p) (`_key_space`).  Same buffers, parameters and state_dict() keys as the one-table cached
         module; defaults cache_size = int(0.1 * sum_k E_k), hashtbl_size = sum_k E_k.  Warm-up counts the batch's keys in one
@@ -156,11 +159,12 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         from tt_embeddings_ops import _SGD_LIKE, BufferList
         self.tt_cores = nn.ParameterList()
         self.optimizer_state = BufferList("optimizer_state")
-        stateful = optimizer not in _SGD_LIKE
+        stateful = optimizer not in _SGD_LIKE and (sparse or optimizer != OptimType.EXACT_ADAM)  # (Adam's state: with sparse=True only)
         for t in range(nd):
             shape = (1, sum(p[t] for p in ps), self.tt_ranks[t] * self.tt_q_shapes[t] * self.tt_ranks[t + 1])
             self.tt_cores.append(nn.Parameter(torch.empty(shape, device=device, dtype=torch.float32)))
             self.optimizer_state.append(torch.zeros(shape if stateful else 0, device=device, dtype=torch.float32))
+        self._init_adam(betas, weight_decay, decoupled_weight_decay, use_cache)
         # every table is initialised as a table of its own cardinality would be
         self.table_ranks = None if table_ranks is None else [[1] + [int(x) for x in rk] + [1] for rk in table_ranks]
         if self.table_ranks is not None:
@@ -322,6 +326,22 @@ def _lookup_node(fn):
     return fn
 
 
+def _adam_node(fn, depth: int = 4):
+    """under OptimType.EXACT_ADAM the node that enqueues a group's LAST backward kernels is not the lookup node but the
+    `_AdamStepFunction` node the cores passed through, a few edges below it (behind the view / pad nodes of the q0 > 4 routes):
+    that node, or None"""
+    todo = [(fn, 0)]
+    while todo:
+        f, d = todo.pop()
+        if f is None:
+            continue
+        if "_AdamStepFunction" in type(f).__name__:
+            return f
+        if d < depth:
+            todo += [(g, d + 1) for g, _ in f.next_functions]
+    return None
+
+
 class MixedTTEmbeddingBag(nn.Module):
     """TT embedding bags for tables of different cardinality -- and, table by table, different TT ranks and different
     factorings q of the (common) embedding dimension.
@@ -365,8 +385,14 @@ class MixedTTEmbeddingBag(nn.Module):
                  streams: bool = False, fused: bool = False, pad_ranks: Optional[bool] = None,
                  pad_q: Optional[bool] = None, mode: str = "sum", padding_idx=None, use_cache: bool = False,
                  cache_size: int = 0, hashtbl_size: int = 0, deterministic_cache_update: Optional[bool] = None,
-                 dense_below: int = 0, dense: Optional[Sequence[bool]] = None) -> None:
+                 dense_below: int = 0, dense: Optional[Sequence[bool]] = None, betas: Tuple[float, float] = (0.9, 0.999),
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False) -> None:
         super().__init__()
+        if use_cache and sparse and optimizer == OptimType.EXACT_ADAM:
+            raise NotImplementedError("OptimType.EXACT_ADAM does not support use_cache=True (the cache rows have no Adam state)")
+        # (betas, weight_decay, decoupled_weight_decay: handed to every group; read under OptimType.EXACT_ADAM only -- one fused
+        #  Adam / AdamW step per group and backward)
+        adam_kw = dict(betas=betas, weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
         if use_cache and not fused:
             raise NotImplementedError("use_cache=True needs fused=True: the row cache is one per fused group "
                                       "(VarTableTTEmbeddingBag(use_cache=True))")
@@ -483,12 +509,12 @@ class MixedTTEmbeddingBag(nn.Module):
                     [self.num_embeddings[k] for k in tables], self.embedding_dim, rmax, [list(shapes[k]) for k in tables],
                     qmax, optimizer, learning_rate, eps, sparse, weight_dist, enforce_embedding_dim, device, True,
                     [ranks[k] for k in tables] if mixed_ranks else None, [qs[k] for k in tables] if mixed_q else None, mode,
-                    **cache_kw))
+                    **cache_kw, **adam_kw))
             else:
                 self.groups.append(TableBatchedTTEmbeddingBag(
                     len(tables), max(self.num_embeddings[k] for k in tables), self.embedding_dim, list(ranks[k0]),
                     list(shapes[k0]), qs[k0], optimizer, learning_rate, eps, sparse, False, 0, 0, weight_dist,
-                    enforce_embedding_dim, device, True, mode=mode))
+                    enforce_embedding_dim, device, True, mode=mode, **adam_kw))
         # A group module takes ONE padding value, its tables may each have their own: forward() rewrites every table's padding
         # slots to PAD_SENTINEL and the group compacts on that.  The sentinel is no valid row, so it is handed over here -- the
         # one place -- past the constructor's normalisation, which would read -1 as "the last row".
@@ -502,7 +528,7 @@ class MixedTTEmbeddingBag(nn.Module):
         self.dense_group_tables = dense_table_groups(self.dense_tables)
         self.dense_groups = nn.ModuleList(
             DenseTableBatchedEmbeddingBag([self.num_embeddings[k] for k in tables], self.embedding_dim, optimizer, learning_rate,
-                                          eps, sparse, device, True, mode) for tables in self.dense_group_tables)
+                                          eps, sparse, device, True, mode, **adam_kw) for tables in self.dense_group_tables)
 
     # ------------------------------------------------------------------ the groups' row caches (use_cache=True)
     def cache_populate(self, keep_trained: bool = False, freq_shift: int = 0) -> None:
@@ -595,6 +621,8 @@ class MixedTTEmbeddingBag(nn.Module):
                 with torch.cuda.stream(s):
                     res = mod(idx, off, True, psw)  # [tables, B, D]
                 node = _lookup_node(res.grad_fn)
+                if node is not None and mod.__dict__.get("_adam") is not None:
+                    node = _adam_node(node) or node  # (the Adam step is enqueued behind the lookup's backward: join after it)
                 if node is not None:
                     # autograd runs this group's backward (recompute + fused optimizer) on the group's stream as well, and
                     # with a fused optimizer there is no leaf gradient whose stream the engine would join at the end: join

@@ -853,6 +853,33 @@ int ttx_dense_bags_backward(int32_t optim, int32_t num_tables, int64_t B, int32_
                             ttx_stream_t stream);
 int ttx_dense_bags_info(int32_t D, int64_t nnz, int32_t* out);
 
+/* ---- fused Adam (csrc/ttx_adam.hip; not in the reference) -------------------------------------------------
+ * One call is ONE optimizer step of torch.optim.Adam / AdamW (no amsgrad) over up to TTX_ADAM_MAX_TENSORS dense float32 tensors:
+ * the cores of a TT module (their dense gradients from the TTX_OPTIM_DENSE routes), or the weight of a dense group.  Every
+ * element steps, whatever its gradient.  numel, w, g, m, v are HOST arrays of ntensors entries (sizes, and device pointers to
+ * weights, gradients, exp_avg, exp_avg_sq) read during the call: they travel in the kernel arguments.  step is a DEVICE int64 [1],
+ * the number of steps taken so far.
+ * CONTRACT
+ *   update      with t = *step + 1, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t (in double), per element: decoupled != 0 and
+ *               weight_decay != 0: w *= 1 - lr wd first;  g' = g, or g + wd w when weight_decay != 0 and decoupled == 0;
+ *               m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  w -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
+ *               After the call *step == t.  The tensors of a call must not overlap; g is only read.
+ *   step        MECHANISM: a one-thread launch in front advances *step and leaves lr / bc1 and 1 / sqrt(bc2) in the workspace; the
+ *               element launch reads those two floats only.  No work-group reads a step another one has advanced; nothing is read
+ *               back, nothing allocated: capturable, and a replayed graph advances *step as eager calls do (lr and the other
+ *               scalars are baked into a captured call).  Two launches per call.
+ *   paths       16-byte accesses on the full chunks of a tensor whose four pointers are 16-byte aligned, scalars on its tail and
+ *               on a misaligned tensor; grid capped at 2,048 work-groups, grid-stride beyond.  A zero-size tensor is legal.
+ *   errors      -1 with ttx_last_error() set, before anything touches a device: ntensors outside [0, TTX_ADAM_MAX_TENSORS], a
+ *               negative size, a NULL pointer that would be read, a pointer not 4-byte aligned (step: 8-byte), a beta outside
+ *               [0, 1), eps < 0, a workspace smaller than ttx_adam_apply_workspace_bytes(ntensors).  ntensors == 0, or every size
+ *               zero: returns 0, launches nothing and leaves *step alone (step and workspace may then be NULL). */
+#define TTX_ADAM_MAX_TENSORS 16
+size_t ttx_adam_apply_workspace_bytes(int32_t ntensors);
+int ttx_adam_apply(int32_t ntensors, const int64_t* numel, float* const* w, const float* const* g, float* const* m,
+                   float* const* v, int64_t* step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   int32_t decoupled, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
