@@ -34,6 +34,9 @@ Deliberate differences (each is a superset or a fix):
     reference asserts one table, :456) keys one hash table / cache_weight by table * prod(tt_p_shapes) + index
     (TTTablesCachedLookupFunction below), on the ctypes route -- and, for tables of different row factors
     (ttx_mixed.VarTableTTEmbeddingBag(use_cache=True), DESIGN.md 4.14), by key_base[table] + index through the same node;
+  * nn.EmbeddingBag.from_pretrained's counterpart: the classmethod `from_pretrained` (TT-SVD of dense tables, ttx_svd.py),
+    `truncate_ranks` (TT rounding into a new module), `table_cores` / `load_table_cores` (one table's cores in a
+    layout-independent form) and `full_weight(table)` for any number of tables (DESIGN.md 4.18);
   * when ttx_torch.so is built the lookup runs as a C++ autograd node (same C ABI
     calls as TTLookupFunction below, which stays the reference-shaped route); with a
     live cache that node keeps the partition's split point on the device instead of
@@ -55,6 +58,7 @@ import torch
 from torch import nn
 
 import tt_embeddings as _engine  # the 11-function native-module surface
+import ttx_svd as _svd  # TT-SVD / rounding behind from_pretrained and truncate_ranks (pure torch)
 
 _native = None  # ttx_torch (csrc/ttx_torch.cpp), False once an import attempt failed
 
@@ -778,6 +782,18 @@ def suggested_tt_shapes(n: int, d: int = 3, allow_round_up: bool = True) -> List
 # modules
 # --------------------------------------------------------------------------- #
 
+def _check_module_kwargs(cls, kw: dict) -> None:
+    """from_pretrained's `module_kwargs` against `cls`'s constructor, before the (long) factorisation: a TypeError for a keyword
+    it does not take (`freeze`: the modules train) or that from_pretrained sets itself"""
+    import inspect
+
+    own = ("self", "num_tables", "num_embeddings", "embedding_dim", "tt_ranks", "tt_p_shapes", "tt_q_shapes")
+    known = [n for n in inspect.signature(cls.__init__).parameters if n not in own]
+    for name in kw:
+        if name not in known:
+            raise TypeError(f"{cls.__name__}.from_pretrained() got an unexpected keyword argument {name!r}")
+
+
 class TableBatchedTTEmbeddingBag(nn.Module):
     """`num_tables` TT-compressed embedding tables of identical shape looked up
     in one pass (sum pooling -- or `mode="mean"` / `"max"` --, include_last_offset form: offsets has
@@ -953,9 +969,141 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                    self.optimizer_step, self.learning_rate, self.eps, self._adam)
 
     # ------------------------------------------------------------------ init
-    def full_weight(self) -> torch.Tensor:
+    def full_weight(self, table: Optional[int] = None) -> torch.Tensor:
+        """`table` None: the one table of a one-table module expanded to [prod(tt_p_shapes), D] (the reference's).  An integer (not
+        in the reference): that table's [num_embeddings, D], of any number of tables."""
+        if table is not None:
+            return _svd.tt_full(self.table_cores(table), self.num_embeddings)
         assert self.num_tables == 1, "full_weight() only supported for num_tables == 1 for now"
         return tt_matrix_to_full(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), [1, 0, 2, 3])
+
+    # ------------------------------------------------- canonical cores, from_pretrained, truncate_ranks (DESIGN.md 4.18)
+    def _table_index(self, table: int) -> int:
+        if isinstance(table, bool) or not hasattr(table, "__index__") or not -self.num_tables <= int(table) < self.num_tables:
+            raise IndexError(f"table {table!r}: the module has {self.num_tables} table(s)")
+        return int(table) % self.num_tables
+
+    def table_cores(self, table: int = 0) -> List[torch.Tensor]:
+        """one table's cores in the layout-independent CANONICAL form of ttx_svd: core k [r_k, p_k, q_k, r_{k+1}], copies"""
+        k = self._table_index(table)
+        return _svd.from_module_layout([c.detach()[k] for c in self.tt_cores], self.tt_q_shapes, self.tt_ranks)
+
+    def _check_loadable(self, cores, p: Sequence[int], q: Sequence[int], ranks: Sequence[int], exact: bool) -> List[int]:
+        """canonical `cores` against one table's geometry -> their [r_0 .. r_T]; `exact`: the ranks must be `ranks`, else at most"""
+        if len(cores) != len(p):
+            raise ValueError(f"{len(p)} cores expected, got {len(cores)}")
+        got = _svd._check_cores(cores)
+        for t, c in enumerate(cores):
+            if int(c.size(1)) != p[t] or int(c.size(2)) != q[t]:
+                raise ValueError(f"core {t}: expected [r, {p[t]}, {q[t]}, r'], got {list(c.shape)}")
+        if (got != list(ranks)) if exact else any(a > b for a, b in zip(got, ranks)):
+            raise ValueError(f"the cores' ranks {got[1:-1]} do not fit the module's {list(ranks)[1:-1]}")
+        if self.use_cache and not self.warmup:
+            raise RuntimeError("load_table_cores with a live cache: the cached rows would no longer belong to the cores "
+                               "(reset_cache() first)")
+        return got
+
+    def load_table_cores(self, cores: Sequence[torch.Tensor], table: int = 0) -> None:
+        """write one table's cores from the canonical form (`table_cores`' / ttx_svd's), shapes checked; optimizer state and
+        cache are left as they are (a live cache is refused)"""
+        k = self._table_index(table)
+        self._check_loadable(cores, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, exact=True)
+        with torch.no_grad():
+            for dst, src in zip(self.tt_cores, _svd.to_module_layout(cores)):
+                dst[k].copy_(src)
+
+    _STACKED_TABLES = True  # from_pretrained takes [num_tables, E, D] (the one-table modules: [E, D])
+
+    @classmethod
+    def _construct(cls, num_embeddings, embedding_dim: int, tt_ranks, tt_p_shapes, tt_q_shapes, kw: dict):
+        """the ordinary constructor behind from_pretrained / truncate_ranks; `num_embeddings`: one cardinality per table"""
+        return cls(len(num_embeddings), num_embeddings[0], embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, **kw)
+
+    @staticmethod
+    def _pretrained_tables(embeddings, stacked: bool) -> List[torch.Tensor]:
+        """`embeddings` -> one [E, D] tensor per table, checked (ValueError) before any arithmetic"""
+        if isinstance(embeddings, torch.Tensor):
+            if embeddings.dim() != (3 if stacked else 2):
+                raise ValueError(f"embeddings: a tensor {'[num_tables, E, D] or a list of [E, D]' if stacked else '[E, D]'}, "
+                                 f"got {list(embeddings.shape)}")
+            tables = list(embeddings.unbind(0)) if stacked else [embeddings]
+        else:
+            tables = list(embeddings)
+        if not tables or any(not isinstance(w, torch.Tensor) or w.dim() != 2 or not w.is_floating_point() for w in tables):
+            raise ValueError("embeddings: 2-D floating-point tables [E, D]")
+        if len({int(w.size(1)) for w in tables}) != 1:
+            raise ValueError("embeddings: every table needs the same embedding dimension")
+        return tables
+
+    @staticmethod
+    def _pretrained_dims(tt_ranks, tt_p_shapes, tt_q_shapes) -> int:
+        """the number of cores from_pretrained factors into: what the given ranks / shapes say, else the constructors' three"""
+        for v, extra in ((tt_ranks, 1), (tt_p_shapes, 0), (tt_q_shapes, 0)):
+            if v is not None:
+                return len(v) + extra
+        return 3
+
+    @classmethod
+    def from_pretrained(cls, embeddings, tt_ranks: Optional[Sequence[int]] = None, tt_p_shapes: Optional[List[int]] = None,
+                        tt_q_shapes: Optional[List[int]] = None, *, rel_error: Optional[float] = None,
+                        max_rank: Optional[int] = None, rank_multiple: int = 1, **module_kwargs):
+        """nn.EmbeddingBag.from_pretrained's counterpart (not in the reference): the module whose tables are the
+        TT-SVD (ttx_svd.tt_svd) of the dense tables `embeddings` -- [num_tables, E, D] or a list of [E, D] for the batched module,
+        [E, D] for the one-table modules.  `tt_ranks`: the module's ranks, exactly (`rel_error` / `max_rank` / `rank_multiple`
+        instead: chosen per table for ||W - TT||_F <= rel_error ||W||_F, the module built at the per-position maximum and every
+        table zero-padded to it).  `tt_p_shapes` / `tt_q_shapes` default as in the constructor; `module_kwargs` are the
+        constructor's (optimizer, sparse, use_cache, mode, padding_idx, device, ...).  The factorisation runs where `embeddings`
+        lives.  The module is built by its constructor -- optimizer state zero, a cache in warm-up -- and its cores are loaded;
+        `module.compression` lists (ranks, bound, norm) per table.  There is no `freeze`: the result trains like any module."""
+        _check_module_kwargs(cls, module_kwargs)
+        tables = cls._pretrained_tables(embeddings, stacked=cls._STACKED_TABLES)
+        if len({int(w.size(0)) for w in tables}) != 1:
+            raise ValueError("embeddings: the tables of a batched module share one shape (ttx_mixed.VarTableTTEmbeddingBag: any)")
+        E, D = int(tables[0].size(0)), int(tables[0].size(1))
+        nd = cls._pretrained_dims(tt_ranks, tt_p_shapes, tt_q_shapes)
+        p = [int(x) for x in tt_p_shapes] if tt_p_shapes is not None else suggested_tt_shapes(E, nd)
+        q = [int(x) for x in tt_q_shapes] if tt_q_shapes is not None \
+            else suggested_tt_shapes(D, nd, allow_round_up=not module_kwargs.get("enforce_embedding_dim", False))
+        res = [_svd.tt_svd(w, p, q, tt_ranks, rel_error=rel_error, max_rank=max_rank, rank_multiple=rank_multiple) for w in tables]
+        return cls._from_factors(res, [E] * len(tables), D, p, q, module_kwargs)
+
+    @classmethod
+    def _from_factors(cls, res, num_embeddings, D: int, p, q, kw: dict):
+        ranks = _svd.merged_ranks(res)
+        kw = dict(kw)
+        kw.setdefault("weight_dist", "uniform")  # (the cheapest initialiser: the cores are overwritten)
+        m = cls._construct(num_embeddings, D, ranks, p, q, kw)
+        for k, r in enumerate(res):
+            m.load_table_cores(_svd.tt_pad_ranks(r.cores, ranks), k)
+        m.compression = [(list(r.ranks), r.bound, r.norm) for r in res]
+        return m
+
+    def _ctor_kwargs(self) -> dict:
+        """the constructor's keywords as this module was built (ranks and shapes apart)"""
+        adam = self.__dict__.get("_adam") or (0.9, 0.999, 0.0, False)
+        kw = dict(optimizer=self.optimizer, learning_rate=self.learning_rate, eps=self.eps, sparse=self.sparse,
+                  use_cache=bool(self.use_cache), device=self.tt_cores[0].device, include_last_offset=self.include_last_offset,
+                  dedup=self.dedup, reference_exact_populate=self.reference_exact_populate,
+                  deterministic_cache_update=self.deterministic_cache_update, mode=self.mode, padding_idx=self.padding_idx,
+                  betas=(adam[0], adam[1]), weight_decay=adam[2], decoupled_weight_decay=adam[3])
+        if self.use_cache:
+            kw.update(cache_size=int(self.cache_weight.size(0)), hashtbl_size=int(self.hashtbl.numel()))
+        return kw
+
+    def truncate_ranks(self, new_ranks: Optional[Sequence[int]] = None, *, rel_error: Optional[float] = None,
+                       max_rank: Optional[int] = None, rank_multiple: int = 1):
+        """-> a NEW module of the same constructor arguments at lower TT ranks (not in the reference): every table
+        rounded by ttx_svd.tt_round -- to `new_ranks`, or per table for `rel_error` (the module at the per-position maximum).
+        Not in place: the Parameters' shapes and the registered state change with the ranks.  Optimizer state starts at zero; a
+        LIVE cache is refused (its rows would no longer belong to the cores: reset_cache() first); `compression` as
+        from_pretrained's, against the tables this module holds."""
+        if self.use_cache and not self.warmup:
+            raise RuntimeError("truncate_ranks with a live cache: the cached rows would no longer belong to the cores "
+                               "(reset_cache() first)")
+        res = [_svd.tt_round(self.table_cores(k), new_ranks, rel_error=rel_error, max_rank=max_rank, rank_multiple=rank_multiple)
+               for k in range(self.num_tables)]
+        return type(self)._from_factors(res, [self.num_embeddings] * self.num_tables, self.embedding_dim, list(self.tt_p_shapes),
+                                        list(self.tt_q_shapes), self._ctor_kwargs())
 
     def _assign(self, t: int, values: np.ndarray) -> None:
         core = self.tt_cores[t]
@@ -1810,6 +1958,14 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                          enforce_embedding_dim, device, include_last_offset, dedup, reference_exact_populate,
                          deterministic_cache_update, mode, padding_idx, betas, weight_decay, decoupled_weight_decay)
 
+    _STACKED_TABLES = False
+
+    @classmethod
+    def _construct(cls, num_embeddings, embedding_dim: int, tt_ranks, tt_p_shapes, tt_q_shapes, kw: dict):
+        if len(num_embeddings) != 1:
+            raise ValueError(f"{cls.__name__} holds one table, got {len(num_embeddings)}")
+        return cls(num_embeddings[0], embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, **kw)
+
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # squeeze is a view both ways: `[0]` would make autograd materialise a zero [1,B,D] buffer
@@ -1864,6 +2020,12 @@ class TTEmbedding(TTEmbeddingBag):
                          reference_exact_populate=reference_exact_populate, deterministic_cache_update=deterministic_cache_update,
                          mode="sum", padding_idx=padding_idx, betas=betas, weight_decay=weight_decay,
                          decoupled_weight_decay=decoupled_weight_decay)
+
+    def _ctor_kwargs(self) -> dict:
+        kw = super()._ctor_kwargs()
+        for name in ("include_last_offset", "mode"):  # (not this constructor's)
+            kw.pop(name)
+        return kw
 
     def prefetch(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> bool:
         return False  # (no prologue to plan ahead: there are no bags)

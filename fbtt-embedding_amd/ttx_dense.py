@@ -123,6 +123,22 @@ class DenseTableBatchedEmbeddingBag(nn.Module):
                 self.optimizer_state_v.zero_()
                 self.optimizer_step.zero_()
 
+    @classmethod
+    def from_pretrained(cls, embeddings: Sequence[torch.Tensor], **module_kwargs) -> "DenseTableBatchedEmbeddingBag":
+        """the module whose table k holds the rows of `embeddings[k]` [E_k, D] (copied); `module_kwargs` are the constructor's.
+        Beside the TT modules' from_pretrained; there is no `freeze`."""
+        _ops._check_module_kwargs(cls, module_kwargs)
+        tables = list(embeddings) if not isinstance(embeddings, torch.Tensor) else None
+        if not tables or any(not isinstance(w, torch.Tensor) or w.dim() != 2 or not w.is_floating_point() for w in tables):
+            raise ValueError("embeddings: a list of 2-D floating-point tables [E_k, D]")
+        if len({int(w.size(1)) for w in tables}) != 1:
+            raise ValueError("embeddings: every table needs the same embedding dimension")
+        m = cls([int(w.size(0)) for w in tables], int(tables[0].size(1)), **module_kwargs)
+        with torch.no_grad():
+            for k, w in enumerate(tables):
+                m.table_weight(k).copy_(w)
+        return m
+
     def table_weight(self, k: int) -> torch.Tensor:
         """table k's rows [E_k, D], a view of `weight` (`table_weight(k).copy_(bag.weight)` imports an nn.EmbeddingBag)"""
         return self.weight.detach()[self.row_base[k]:self.row_base[k + 1]]

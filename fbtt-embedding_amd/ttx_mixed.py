@@ -286,8 +286,78 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         sizes = [p[t] for p in self.tt_p_shapes]
         return list(torch.split(self.tt_cores[t].detach()[0], sizes, dim=0))
 
-    def full_weight(self) -> torch.Tensor:
-        raise NotImplementedError("full_weight() is per table: build a TTEmbeddingBag from table_rows()")
+    def full_weight(self, table: Optional[int] = None) -> torch.Tensor:
+        """`table` = k: table k's [E_k, D]; None: refused, as the tables have no common shape"""
+        if table is None:
+            raise NotImplementedError("full_weight() is per table: full_weight(k), or build a TTEmbeddingBag from table_rows()")
+        k = self._table_index(table)
+        return _ops._svd.tt_full(self.table_cores(k), self.table_num_embeddings[k])
+
+    # ------------------------------------------------- canonical cores, from_pretrained (DESIGN.md 4.18)
+    def _no_table_q(self, what: str) -> None:
+        if self.table_q is not None:
+            raise NotImplementedError(f"{what} is not offered for a group of differently factored tables (table_q / pad_q): its "
+                                      f"cores are stored padded to the common factoring")
+
+    def table_cores(self, table: int = 0) -> List[torch.Tensor]:
+        """table k's cores in ttx_svd's canonical form [r_k, p_k, q_k, r_{k+1}], copies -- at the table's own ranks
+        (`table_ranks`), else the module's"""
+        self._no_table_q("table_cores")
+        k = self._table_index(table)
+        rk = self.tt_ranks if self.table_ranks is None else self.table_ranks[k]
+        return _ops._svd.from_module_layout([self.table_core(k, t) for t in range(self.tt_ndim)], self.tt_q_shapes, rk)
+
+    def load_table_cores(self, cores: Sequence[torch.Tensor], table: int = 0) -> None:
+        """write table k's cores from the canonical form, shapes checked.  Their ranks may be smaller than the module's (than
+        `table_ranks[k]`, where given): the factor goes into the leading block of the table's slices, the rest is zero -- and
+        stays zero under the fused optimizers, as the padding of `table_ranks` does."""
+        self._no_table_q("load_table_cores")
+        k = self._table_index(table)
+        rk = self.tt_ranks if self.table_ranks is None else self.table_ranks[k]
+        got = self._check_loadable(cores, self.tt_p_shapes[k], self.tt_q_shapes, rk, exact=False)
+        with torch.no_grad():
+            for t, c in enumerate(cores):
+                rows = self.table_rows(t)[k]
+                rows.zero_()
+                rows.view(-1, self.tt_ranks[t], self.tt_q_shapes[t], self.tt_ranks[t + 1])[:, :got[t], :, :got[t + 1]] = \
+                    c.permute(1, 0, 2, 3).to(rows)
+
+    @classmethod
+    def _construct(cls, num_embeddings, embedding_dim: int, tt_ranks, tt_p_shapes, tt_q_shapes, kw: dict):
+        return cls(num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, **kw)
+
+    @classmethod
+    def from_pretrained(cls, embeddings, tt_ranks: Optional[Sequence[int]] = None,
+                        tt_p_shapes: Optional[Sequence[Optional[List[int]]]] = None, tt_q_shapes: Optional[List[int]] = None, *,
+                        rel_error: Optional[float] = None, max_rank: Optional[int] = None, rank_multiple: int = 1,
+                        **module_kwargs):
+        """the parent's from_pretrained for tables of different cardinality: `embeddings` is a list with [E_k, D] per table,
+        `tt_p_shapes` one list per table (or None: the constructor's default).  With `rel_error` every table is truncated at
+        its own ranks and zero-padded to the per-position maximum, at which the module is built."""
+        for name in ("table_q", "table_ranks"):
+            if module_kwargs.get(name) is not None:
+                raise NotImplementedError(f"from_pretrained does not take {name}: every table is factored at the module's "
+                                          f"tt_q_shapes, and smaller ranks are zero-padded")
+        _ops._check_module_kwargs(cls, module_kwargs)
+        if isinstance(embeddings, torch.Tensor):
+            raise ValueError("embeddings: a list with one table [E_k, D] each")
+        tables = cls._pretrained_tables(embeddings, stacked=False)
+        D = int(tables[0].size(1))
+        nd = cls._pretrained_dims(tt_ranks, tt_p_shapes[0] if tt_p_shapes is not None and tt_p_shapes[0] is not None else None,
+                                  tt_q_shapes)
+        if tt_p_shapes is not None and len(tt_p_shapes) != len(tables):
+            raise ValueError(f"tt_p_shapes: one list per table ({len(tables)}), got {len(tt_p_shapes)}")
+        ps = [[int(x) for x in tt_p_shapes[k]] if tt_p_shapes is not None and tt_p_shapes[k] is not None
+              else suggested_tt_shapes(int(w.size(0)), nd) for k, w in enumerate(tables)]
+        q = [int(x) for x in tt_q_shapes] if tt_q_shapes is not None \
+            else suggested_tt_shapes(D, nd, allow_round_up=not module_kwargs.get("enforce_embedding_dim", False))
+        res = [_ops._svd.tt_svd(w, p, q, tt_ranks, rel_error=rel_error, max_rank=max_rank, rank_multiple=rank_multiple)
+               for w, p in zip(tables, ps)]
+        return cls._from_factors(res, [int(w.size(0)) for w in tables], D, ps, q, module_kwargs)
+
+    def truncate_ranks(self, *a, **kw):
+        raise NotImplementedError("truncate_ranks is offered on the one-table and the uniform batched modules: round the tables "
+                                  "with ttx_svd.tt_round(table_cores(k), ..) and load them into a new module")
 
 
 PAD_SENTINEL = -1  # what a table's padding slots become in a group's merged batch: no row of any table
@@ -529,6 +599,94 @@ class MixedTTEmbeddingBag(nn.Module):
         self.dense_groups = nn.ModuleList(
             DenseTableBatchedEmbeddingBag([self.num_embeddings[k] for k in tables], self.embedding_dim, optimizer, learning_rate,
                                           eps, sparse, device, True, mode, **adam_kw) for tables in self.dense_group_tables)
+
+    # ------------------------------------------------------------------ per-table access, from_pretrained
+    def _member(self, table: int):
+        """-> (the group module that holds table k, its position there, whether the group is a dense one)"""
+        n = len(self.num_embeddings)
+        if isinstance(table, bool) or not hasattr(table, "__index__") or not -n <= int(table) < n:
+            raise IndexError(f"table {table!r}: the module has {n} tables")
+        k = int(table) % n
+        for mods, ids, dense in ((self.groups, self.group_tables, False),
+                                 (self.__dict__["_modules"].get("dense_groups", ()), self.__dict__.get("dense_group_tables", ()), True)):
+            for mod, tables in zip(mods, ids):
+                if k in tables:
+                    return mod, tables.index(k), dense
+        raise AssertionError(f"table {k} belongs to no group")
+
+    def table_cores(self, table: int) -> List[torch.Tensor]:
+        """TT table k's cores in ttx_svd's canonical form (copies)"""
+        mod, j, dense = self._member(table)
+        if dense:
+            raise ValueError(f"table {table} is a dense member: it has rows (full_weight), not cores")
+        return mod.table_cores(j)
+
+    def load_table_cores(self, cores: Sequence[torch.Tensor], table: int) -> None:
+        """write TT table k's cores from the canonical form (in a fused group: ranks up to the group's, zero-padded)"""
+        mod, j, dense = self._member(table)
+        if dense:
+            raise ValueError(f"table {table} is a dense member: it has rows, not cores")
+        mod.load_table_cores(cores, j)
+
+    def full_weight(self, table: int) -> torch.Tensor:
+        """table k's [E_k, D]: expanded from its cores, or -- a dense member -- a copy of its rows"""
+        mod, j, dense = self._member(table)
+        if dense:
+            return mod.table_weight(j).clone()
+        return mod.full_weight(j)[:self.num_embeddings[int(table) % len(self.num_embeddings)]]
+
+    @classmethod
+    def from_pretrained(cls, embeddings, tt_ranks=None, tt_p_shapes: Optional[Sequence[Optional[List[int]]]] = None,
+                        tt_q_shapes=None, *, rel_error: Optional[float] = None, max_rank: Optional[int] = None,
+                        rank_multiple: int = 1, **module_kwargs):
+        """nn.EmbeddingBag.from_pretrained's counterpart: `embeddings` is a list with [E_k, D] per table; the TT
+        members are the TT-SVD of their tables (ttx_svd.tt_svd), the dense members (`dense_below=` / `dense=`) copies of their
+        rows.  `tt_ranks`: one list or one per table, as in the constructor; `rel_error` (with `max_rank` / `rank_multiple`)
+        instead: every table gets the ranks its own truncation chose, three cores unless the shapes given say otherwise.
+        `module_kwargs` are the constructor's.  `module.compression[k]` = (ranks, bound, norm), None for a dense member."""
+        _ops._check_module_kwargs(cls, module_kwargs)
+        if isinstance(embeddings, torch.Tensor):
+            raise ValueError("embeddings: a list with one table [E_k, D] each")
+        tables = TableBatchedTTEmbeddingBag._pretrained_tables(embeddings, stacked=False)
+        n, D = len(tables), int(tables[0].size(1))
+        Es = [int(w.size(0)) for w in tables]
+        if (tt_ranks is None) == (rel_error is None):
+            raise ValueError("exactly one of tt_ranks and rel_error must be given")
+        dense = dense_table_flags(Es, module_kwargs.get("dense_below", 0), module_kwargs.get("dense"))
+        per_table = lambda v: v is not None and len(v) > 0 and isinstance(v[0], (list, tuple))  # noqa: E731
+        if tt_ranks is not None:
+            ranks = [list(r) for r in tt_ranks] if per_table(tt_ranks) else [list(tt_ranks)] * n
+            nds = [len(r) + 1 for r in ranks]
+        else:
+            shapes = list(tt_p_shapes or []) + (list(tt_q_shapes) if per_table(tt_q_shapes) else [tt_q_shapes])
+            given = [v for v in shapes if v is not None]
+            ranks, nds = [None] * n, [len(given[0]) if given else 3] * n
+        if len(ranks) != n or (tt_p_shapes is not None and len(tt_p_shapes) != n):
+            raise ValueError(f"tt_ranks / tt_p_shapes: one entry per table ({n})")
+        qs = [list(v) for v in tt_q_shapes] if per_table(tt_q_shapes) else [None if tt_q_shapes is None else list(tt_q_shapes)] * n
+        res: List[Optional[_ops._svd.TTFactors]] = [None] * n
+        for k, w in enumerate(tables):
+            if dense[k]:
+                continue
+            p = tt_p_shapes[k] if tt_p_shapes is not None and tt_p_shapes[k] is not None else suggested_tt_shapes(Es[k], nds[k])
+            q = qs[k] if qs[k] is not None else suggested_tt_shapes(
+                D, nds[k], allow_round_up=not module_kwargs.get("enforce_embedding_dim", False))
+            res[k] = _ops._svd.tt_svd(w, p, q, ranks[k], rel_error=rel_error, max_rank=max_rank, rank_multiple=rank_multiple)
+        if tt_ranks is None:  # every table at the ranks its truncation chose (a dense member's entry is not read)
+            some = next((r.ranks for r in res if r is not None), [1] * (nds[0] - 1))
+            tt_ranks = [list(r.ranks) if r is not None else list(some) for r in res]
+        kw = dict(module_kwargs)
+        kw.setdefault("weight_dist", "uniform")  # (the cheapest initialiser: the cores are overwritten)
+        m = cls(Es, D, tt_ranks, tt_p_shapes, tt_q_shapes, **kw)
+        with torch.no_grad():
+            for k, w in enumerate(tables):
+                if dense[k]:
+                    mod, j, _ = m._member(k)
+                    mod.table_weight(j).copy_(w)
+                else:
+                    m.load_table_cores(res[k].cores, k)
+        m.compression = [None if r is None else (list(r.ranks), r.bound, r.norm) for r in res]
+        return m
 
     # ------------------------------------------------------------------ the groups' row caches (use_cache=True; DESIGN.md 4.14)
     def cache_populate(self, keep_trained: bool = False, freq_shift: int = 0) -> None:
