@@ -213,6 +213,15 @@ def _load(path):
     L.ttx_adam_apply_workspace_bytes.restype = C.c_size_t
     L.ttx_adam_apply_workspace_bytes.argtypes = [i32]
     L.ttx_adam_apply.argtypes = [i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, i32, vp, sz, vp]
+    # bf16 inference forward
+    L.ttx_tt_rows_bf16_supported.argtypes = [G]
+    L.ttx_tt_pack_bf16_elems.restype = i64
+    L.ttx_tt_pack_bf16_elems.argtypes = [G, i32]
+    L.ttx_tt_pack_bf16.argtypes = [G, i32, vp, vp, vp]
+    L.ttx_tt_rows_bf16_workspace_bytes.restype = C.c_size_t
+    L.ttx_tt_rows_bf16_workspace_bytes.argtypes = [G, i32, i64]
+    L.ttx_tt_rows_bf16.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
     return L
 
 
@@ -1111,6 +1120,70 @@ def tt_rows_p(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tablei
         _check(lb.ttx_tt_rows_p(C.byref(g), D, nnz, indices.data_ptr(), tableidx.data_ptr(), _ptr_array(cores), rows.data_ptr(),
                                 _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
     return rows
+
+
+# ---- bf16 inference forward (include/ttx.h "bf16 inference forward"; the module on top: ttx_infer.TTInferenceBag) ----
+def tt_rows_bf16_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the bf16 rows kernel take this geometry (T = 3, ranks <= 64, ...)?  Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_rows_bf16_supported(C.byref(g)))
+
+
+def pack_cores_bf16(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """the fp32 cores rounded to bf16 (nearest even, as tensor.to(torch.bfloat16)) in the packed layout of the bf16 rows
+    kernel: one flat bfloat16 tensor per core."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(tt_cores[0])
+    cores = _cores(tt_cores, g)
+    lb = lib()
+    out = []
+    with _guard(dev):
+        for t, c in enumerate(cores):
+            n = lb.ttx_tt_pack_bf16_elems(C.byref(g), t)
+            if n <= 0:
+                raise RuntimeError("tt_embeddings: pack_cores_bf16: the bf16 kernel does not take this geometry "
+                                   "(tt_rows_bf16_supported)")
+            pk = torch.empty(n, dtype=torch.bfloat16, device=dev)
+            _check(lb.ttx_tt_pack_bf16(C.byref(g), t, c.data_ptr(), pk.data_ptr(), _stream(dev)))
+            out.append(pk)
+    return out
+
+
+def tt_rows_bf16(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores,
+                 plan: Optional[Plan] = None) -> torch.Tensor:
+    """rows [nnz, D] float32 in lookup order from the packed bf16 cores of pack_cores_bf16; `plan`: the batch's plan
+    (make_plan / lookup_prologue), None: built in the workspace."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(packed_cores[0])
+    if len(packed_cores) != 3 or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
+        raise RuntimeError("tt_embeddings: tt_rows_bf16 needs the three packed bfloat16 cores of pack_cores_bf16 on one device")
+    lb = lib()
+    for t, c in enumerate(packed_cores):
+        if c.numel() != lb.ttx_tt_pack_bf16_elems(C.byref(g), t):
+            raise RuntimeError(f"tt_embeddings: packed core {t} holds {c.numel()} elements, the geometry needs "
+                               f"{lb.ttx_tt_pack_bf16_elems(C.byref(g), t)}")
+    indices = _i64(indices, "indices")
+    nnz = indices.numel()
+    rows = torch.empty((nnz, D), dtype=torch.float32, device=dev)
+    st = _stream(dev)
+    ws = _workspace(dev, st, 0 if plan is not None else lb.ttx_tt_rows_bf16_workspace_bytes(C.byref(g), D, nnz))
+    with _guard(dev):
+        _check(lb.ttx_tt_rows_bf16(C.byref(g), D, nnz, indices.data_ptr(),
+                                   None if tableidx is None else _i64(tableidx, "tableidx").data_ptr(), _ptr_array(packed_cores),
+                                   rows.data_ptr(), _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
+    return rows
+
+
+def bag_sum_pool(rows: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """-> [nb, D]: the fp32 sum of each bag's rows in index order (rows in lookup order, bags contiguous; offsets with
+    their closing entry); an empty bag gives zeros."""
+    dev = _dev(rows)
+    rows, offsets = _f32(rows, "rows"), _i64(offsets, "offsets")
+    nb, D = offsets.numel() - 1, rows.size(1)
+    out = torch.empty((nb, D), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(lib().ttx_bag_sum_pool(nb, D, offsets.data_ptr(), rows.data_ptr(), out.data_ptr(), _stream(dev)))
+    return out
 
 
 def bag_max_pool(rows: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -880,6 +880,59 @@ int ttx_adam_apply(int32_t ntensors, const int64_t* numel, float* const* w, cons
                    float* const* v, int64_t* step, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int32_t decoupled, void* workspace, size_t workspace_bytes, ttx_stream_t stream);
 
+/* ---- bf16 inference forward (csrc/ttx_tt_bf16.hip; not in the reference) --------------------------------
+ * Forward-only lookups of a TRAINED three-core table from bf16 copies of its cores: product 1 (core_0 x core_1) of a pivot
+ * chunk's lookups runs on mfma_f32_16x16x32_bf16 with fp32 accumulation, the last core is contracted per lookup on the VALU
+ * from the fp32 accumulators (x_0 is not rounded).  Nothing here trains, and no existing entry point changes.
+ * SUPPORTED (ttx_tt_rows_bf16_supported: host-side, stateless, touches no device; any p, any num_tables, p_tables or not):
+ *   T == 3, r1 <= 64 and r2 <= 64, q0 <= 16, q1 <= 64, q2 <= 8, and an x_0 tile of at least 16 rows of
+ *   ld = q1 (r2 + 1) rounded up to q1 (mod 64) floats, plus 1 KiB of lookup records, within 128 KiB of LDS (a pass holds 64 rows
+ *   where they fit, else 32 or 16; beside a 64-row tile the pass's core-2 slices are staged in LDS when that keeps the
+ *   work-group within 40 KiB).
+ *   Everything else (T = 2, T = 4, a rank above 64, ...) returns 0 here and TTX_EUNSUPPORTED from the pack and rows calls.
+ * PACKED LAYOUT (owned by this library; all bf16, every slice a multiple of 16 bytes except core 2 with q2 <= 4: 8 bytes):
+ *   K1p = r1 rounded up to 32 (the MFMA's K), N1 = q1 r2, N1p = N1 rounded up to 16, Q2P = 4 if q2 <= 4 else 8; padding is +0.
+ *   core 0   [slices][q0][K1p]     element (a, k1) of a slice at a K1p + k1: the A fragment of row a, 8 k per lane, one 16-byte load
+ *   core 1   [slices][N1p][K1p]    TRANSPOSED: column n = b r2 + k2 of the fp32 slice [r1][q1][r2] holds its K index contiguously
+ *                                  at n K1p + k1: the B fragment of column n is one 16-byte load; columns N1 .. N1p - 1 are zero
+ *   core 2   [slices][r2][Q2P]     element (k2, c) at k2 Q2P + c: the q2 factors of one k2 are one 8 / 16-byte load
+ *   slices = num_tables * p[t] (p_tables: the sum over the tables, table after table), in the order of the fp32 core.
+ *   ttx_tt_pack_bf16_elems(g, t) = slices * elements of a packed slice (0: not supported / bad t); allocate 2 bytes each,
+ *   16-byte aligned.  ttx_tt_pack_bf16 is ONE elementwise launch: round to nearest even, bit for bit tensor.to(torch.bfloat16)
+ *   (a tie goes to the even significand, the largest finite fp32 rounds to Inf, Inf stays, NaN becomes 0x7FC0, subnormals round
+ *   like any other value: nothing is flushed).
+ * ROWS  ttx_tt_rows_bf16: rows [nnz, D] float32, 16-byte aligned, rows[n, :] = the TT row of lookup n in the ORIGINAL lookup
+ *   order, from packed_cores (a HOST array of 3 device pointers).  plan: a plan of ttx_plan_build (with or without bag rows) for
+ *   the same geometry and batch; NULL: built in the workspace (ttx_tt_rows_bf16_workspace_bytes; indices / tableidx as for
+ *   ttx_tt_rows).  With a plan neither indices, tableidx nor the workspace is read.  One work-group per pivot chunk of the plan,
+ *   cores addressed by the plan's slice ids only (clamped to the slices there are) -- which is all a p_tables geometry needs.
+ *   No atomics, one writer per row element: bit-identical from run to run; nothing read back, nothing allocated: capturable.
+ *   nnz == 0 returns 0 and launches nothing.
+ * POOL  ttx_bag_sum_pool: output[b, :] = rows[offsets[b], :] + rows[offsets[b] + 1, :] + ... in index order (fp32, starting
+ *   from +0), b < nb; offsets [nb + 1] int64 (closing entry included), rows in lookup order with contiguous bags.  One writer per
+ *   element, an empty bag gives zeros, any D: 16-byte accesses when D % 4 == 0 and both float pointers are 16-byte aligned, a
+ *   scalar path otherwise.  nb == 0 returns 0 and launches nothing.  The mean is ttx_bag_mean_scale on top.
+ * NUMERICS (inputs: the bf16 cores; c_t below are their exact values).  A product of two bf16 values is exact in fp32, so the
+ *   only roundings are those of fp32 accumulation -- and, for an implementation that feeds x_0 to a second MFMA, ONE rounding of
+ *   x_0 to bf16 (this build does not round x_0; the bound allows it).  Against the float64 chain product on the same cores:
+ *     |err(row[a, b, c])| <= 2^-8 sum_k2 |x_0[(a), (b, k2)]| |c_2[k2, c]|  +  (r1 + r2 + 2) 2^-24 sum_{k1, k2} |c_0| |c_1| |c_2|
+ *   (first term: the unit roundoff of an 8-bit significand on every x_0; second: r1 fp32 additions and r2 fused multiply-adds,
+ *   each with relative error <= 2^-24 of the running sum of absolute values, to first order, with 2 units of slack).
+ *   A pooled element: the sum of its rows' bounds plus len 2^-24 sum |row|.
+ * ERRORS  -1 (TTX_EINVAL) with ttx_last_error() set, before anything touches a device (a p_tables geometry seen for the first
+ *   time places its factors on the device first, as in every p_tables call): a bad geometry, D != prod(q), nnz < 0 or >= 2^31,
+ *   NULL packed cores / rows, NULL indices without a plan, a pointer not 16-byte aligned (packed cores, rows), bag_sum_pool:
+ *   nb < 0 or >= 2^31, D <= 0, a NULL pointer with nb > 0, floats not 4-byte / offsets not 8-byte aligned.  TTX_EWORKSPACE for a
+ *   workspace that is too small (no plan given), TTX_EUNSUPPORTED for a shape ttx_tt_rows_bf16_supported rejects. */
+int ttx_tt_rows_bf16_supported(const ttx_geom* g);
+int64_t ttx_tt_pack_bf16_elems(const ttx_geom* g, int32_t t);
+int ttx_tt_pack_bf16(const ttx_geom* g, int32_t t, const float* core_f32, void* packed, ttx_stream_t stream);
+size_t ttx_tt_rows_bf16_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz);
+int ttx_tt_rows_bf16(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                     const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                     ttx_stream_t stream);
+int ttx_bag_sum_pool(int64_t nb, int32_t D, const int64_t* offsets, const float* rows, float* output, ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
