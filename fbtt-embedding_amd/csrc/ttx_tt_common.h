@@ -3,6 +3,7 @@
 // translation unit so that they compile in parallel -- __graft_entry__.build()).  Inside namespace ttx.
 #pragma once
 #include "ttx_internal.h"
+#include "ttx_magic.h"
 
 namespace ttx {
 
@@ -59,6 +60,16 @@ __device__ __forceinline__ void zero_hot_counters(const Partials& PC) {
   if (blockIdx.x == 0 && PC.hot_cnt)
     for (int i = threadIdx.x; i < PC.n_hot_cnt; i += blockDim.x) PC.hot_cnt[i] = 0;
 }
+// ... for a caller that knows its work-group size as a constant (the single-sub-chunk spec_bwd_kernel): blockDim.x is a load of
+// its own from the argument segment, in front of the loop
+template <int THREADS>
+__device__ __forceinline__ void zero_hot_counters_n(const Partials& PC) {
+  if (blockIdx.x == 0 && PC.hot_cnt) {
+    // (one work-group's few counters: with a constant stride the loop is interleaved and unrolled into three stores and a remainder loop)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (int i = threadIdx.x; i < PC.n_hot_cnt; i += THREADS) PC.hot_cnt[i] = 0;
+  }
+}
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -71,9 +82,15 @@ __device__ __forceinline__ f32x4 mfma1(float a, float b, f32x4 c) {
 
 // the grid also zeroes the pooled output (the bag-pooling kernel that follows accumulates
 // onto it): saves a memset launch
+// (grid: the launch's work-groups where the caller has them in a register already -- gridDim.x is a load of its own from the
+//  argument segment, in front of the loop)
+__device__ __forceinline__ void zero_output(float* __restrict__ out, long long n, unsigned grid) {
+  if (!out) return;
+  for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < n; e += (long long)grid * kThreads) out[e] = 0.f;
+}
 __device__ __forceinline__ void zero_output(float* __restrict__ out, long long n) {
   if (!out) return;
-  for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < n; e += (long long)gridDim.x * kThreads) out[e] = 0.f;
+  zero_output(out, n, gridDim.x);
 }
 
 // test / ablation knobs (include/ttx_test_hooks.h).  They exist in the TEST build only (-DTTX_TEST_HOOKS -> libttx_hooks.so): there

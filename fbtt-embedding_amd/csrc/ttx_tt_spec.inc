@@ -196,6 +196,11 @@ struct RealDims {
   // guarded 4-byte non-temporal stores per lane and kk row of d core_2, lane stride q2 floats, were 263 of the padded backward's
   // 357 us at q = [4,8,16], ranks [24,32].)
   int v4;
+  // (read by the single-sub-chunk kernels) table of pivot slice s = table_quot(s, tmul, tsh) (ttx_magic.h): s / p_1 as the host's
+  // magic pair -- 0 whatever s with one table -- in place of the ~30 instructions of a division between the chunk record and
+  // the lookup records' requests
+  unsigned tmul;
+  int tsh;
 };
 // one guarded element of a padded variant.  (A branch-free form -- load from `p` or from a valid dummy address, select afterwards --
 // was measured slower: ranks [13,12] 0.0456 against 0.0438 ms/step.)
@@ -585,18 +590,42 @@ __device__ __forceinline__ void fwd_load(FwdLoads<S>& L, const FwdRecs<S>& Q, co
 #define TTX_KHEAD_ARGS(P, C)
 #define TTX_KHEAD_ADOPT(P, C) do { } while (0)
 #endif
+// chunk record of work-group b, addressed as pointer + 32-bit byte offset: the scalar load then takes the offset in a register of
+// its own and reads THROUGH the pointer's registers -- the ones it arrived in with the wave -- instead of through a 64-bit sum
+// that has to be formed first (16 b < 2^32: a plan has fewer than 2^28 chunk slots)
+__device__ __forceinline__ int4 chunk_record(const int4* __restrict__ recs, unsigned b) {
+  return *(const int4*)((const char*)recs + b * 16u);
+}
 template <class S, bool MULTI, bool FUSE = false, bool PAD = false>
 __global__ __launch_bounds__(kThreads, S::WGS) void spec_fwd_kernel(TTX_KHEAD_PARAMS Plan P, CorePtrs C, float* __restrict__ rows,
                                                              float* __restrict__ zout, long long nzero, PoolFuse F, RealDims R) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   static_assert(!FUSE || (!MULTI && !PAD), "fused pooling: single sub-chunk, exact shape");
   TTX_KHEAD_ADOPT(P, C);
-  if constexpr (FUSE) zero_empty_bags(F, S::D);
-  else zero_output(zout, nzero);
-  const int4 cr = P.chunk_rec[blockIdx.x];
+  // (the sub-chunk walk zeroes first, as it always did: its entry is paid once per several sub-chunks)
+  constexpr bool EARLY = !MULTI;
+  if constexpr (!EARLY) {
+    if constexpr (FUSE) zero_empty_bags(F, S::D);
+    else zero_output(zout, nzero);
+  }
+  const int4 cr = EARLY ? chunk_record(P.chunk_rec, blockIdx.x) : P.chunk_rec[blockIdx.x];
   // (round 6) the whole record HERE: the compiler fetched its three words one after the other, each in front of the branch that
   // reads it first (length -> slice -> start: three trips of the scalar cache in a row)
-  asm volatile("" ::"s"(cr.x), "s"(cr.y), "s"(cr.z));
+  // (single sub-chunk: ... and with it every argument that does not arrive with the wave and that the path to the first MFMA
+  //  reads.  Left to the compiler, each was fetched in front of its first use and waited for there: the output to zero and its
+  //  length, two dependent trips to the argument segment in FRONT of the chunk record's request, and RealDims::c2n in the
+  //  middle of the operand requests.  All of them are one round of the scalar cache now, the chunk record's.)
+  if constexpr (!EARLY) {
+    asm volatile("" ::"s"(cr.x), "s"(cr.y), "s"(cr.z));
+  } else if constexpr (FUSE) {
+    asm volatile("" ::"s"(cr.x), "s"(cr.y), "s"(cr.z), "s"(rows), "s"(R.c2n), "s"(R.tmul), "s"(R.tsh), "s"(F.arrive), "s"(F.offsets),
+                 "s"(F.rowidx), "s"(F.tableidx), "s"(F.psw), "s"(F.out), "s"(F.B), "s"(F.bags), "s"(F.rows_bytes), "s"(F.dbg));
+    zero_empty_bags(F, S::D);
+  } else {
+    const int grid = P.max_chunks;  // (zero_output's stride: the launch's grid is the plan's chunk slots, an argument like the others)
+    asm volatile("" ::"s"(cr.x), "s"(cr.y), "s"(cr.z), "s"(rows), "s"(zout), "s"(nzero), "s"(R.c2n), "s"(grid));
+    zero_output(zout, nzero, (unsigned)grid);
+  }
   const int s = cr.x, start0 = cr.y, len0 = cr.z;
   if (len0 == 0) return;
   const int lane = lane_id(), w = threadIdx.x / kWave;
@@ -633,7 +662,7 @@ __global__ __launch_bounds__(kThreads, S::WGS) void spec_fwd_kernel(TTX_KHEAD_PA
     const bool has_row = P.hdr[3] != 0;
     const WaveRecs wr = load_recs<S::GPW, S::LPG>(P, start, len, w, has_row);
     if (wr.rec.x >= 0) {
-      const long long tb = F.tableidx ? F.tableidx[wr.rec.x] : (long long)(s / F.p1);
+      const long long tb = F.tableidx ? F.tableidx[wr.rec.x] : (long long)table_quot((unsigned)s, R.tmul, R.tsh);  // (= s / F.p1)
       const long long row = has_row ? (long long)wr.row : F.rowidx[wr.rec.x];
       bag = (int)(tb * F.B + row);
       const long long o0 = F.offsets[bag], o1 = F.offsets[bag + 1];
@@ -1117,18 +1146,34 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
                                                              Partials PC, int dbg, long long* stamps, RealDims R, PStore PS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   TTX_KHEAD_ADOPT(P, C);
-  zero_hot_counters(PC);
   // 16-byte partial stores: d core_0 and the cooperative d core_1 come out transposed.  Not in the sub-chunk walk: its launches hand
   // over more than the Infinity Cache holds, so they stay non-temporal, and the 16-byte layout alone measured 0.2 % slower there
   // (cfg5shard 0.5590 / 0.5597 against 0.5570 / 0.5584 ms per step, profiles/partial_stores.md)
   constexpr bool W16 = S::W16 && !PAD && !MULTI;
   const int chunk = blockIdx.x;
 #define SSTAMP(i) do { if (stamps && threadIdx.x == 0) stamps[(size_t)chunk * 16 + (i)] = wall_clock64(); } while (0)
-  SSTAMP(0);
+  // (the sub-chunk walk enters as it always did: its entry is paid once per several sub-chunks)
+  constexpr bool EARLY = !MULTI;
+  if constexpr (!EARLY) {
+    zero_hot_counters(PC);
+    SSTAMP(0);
+  }
   // (round 6) the plan header's "bag rows valid" word travels WITH the chunk record: read behind the early exit below it was a
   // trip to memory of its own between the chunk record and the bag rows (the branch on it sits in front of their requests)
-  const int4 cr = P.chunk_rec[chunk];
+  const int4 cr = EARLY ? chunk_record(P.chunk_rec, (unsigned)chunk) : P.chunk_rec[chunk];
   const int hdr3 = P.hdr[3];
+  if constexpr (EARLY) {
+    // Single sub-chunk: the chunk record is requested by the wave's first instructions -- its address arrives with the wave --
+    // and UNDER its trip every argument that does not, in one round of the scalar cache.  Left to the compiler each was
+    // fetched in front of its first use and waited for there: the hot counters' and the stamps' pointers in front of the chunk
+    // record's request, the debug mask and then B / p_1 between the chunk record and the lookup records' requests -- four
+    // dependent trips to the argument segment in a chain that holds three trips to memory.  (Stamp 0 is taken behind that round.)
+    asm volatile("" ::"s"(B), "s"(rowidx), "s"(d_output), "s"(dbg), "s"(stamps), "s"(P.ipos[0]), "s"(P.ipos[2]), "s"(PC.pc[0]),
+                 "s"(PC.pc[1]), "s"(PC.pc[2]), "s"(PC.psw), "s"(PC.tableidx), "s"(PC.hot_cnt), "s"(PC.n_hot_cnt), "s"(R.c2n),
+                 "s"(R.tmul), "s"(R.tsh), "s"(PS.flav), "s"(PS.b0), "s"(PS.b1), "s"(PS.b2));
+    zero_hot_counters_n<kThreads>(PC);
+    SSTAMP(0);
+  }
   asm volatile("" ::"v"(cr.x), "v"(cr.y), "v"(cr.z), "v"(cr.w), "v"(hdr3));
   const int s = cr.x, start0 = cr.y, len0 = cr.z;
   if (len0 == 0) return;
@@ -1140,7 +1185,8 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
   float* Aw0 = smem + S::oA + w * S::RG * S::szA;  // this wave's resident regions, one set per group if RG > 1
   float* Xw0 = smem + S::oX + w * S::RG * S::szX;
   float* Gw0 = smem + S::oG + w * S::RG * S::szGb;
-  const int table = PC.tableidx ? (int)PC.tableidx[P.lrec[start0].x] : s / p1;
+  // (single sub-chunk: s / p1 as the host's magic pair -- a multiply-high and a shift, 0 with one table -- RealDims::tmul)
+  const int table = PC.tableidx ? (int)PC.tableidx[P.lrec[start0].x] : (MULTI ? s / p1 : (int)table_quot((unsigned)s, R.tmul, R.tsh));
   const bool has_row = hdr3 != 0;
   const float* B1 = C.c[1] + (size_t)s * (PAD ? R.sl1 : S::SL1);
   float* pc1 = PC.pc[1] + (size_t)cr.w * (PAD ? R.sl1 : S::SL1);  // .w = the chunk's partial slot
@@ -1192,6 +1238,10 @@ __global__ __launch_bounds__(kThreads, (PAD && S::GPP) ? 2 : S::WGS) void spec_b
     bwd_load_recs<S>(rq, P, start, len, w, has_row, rowidx);
 #ifndef TTX_B1_LATE
     spec_fetch_b<S, PAD>(B1, 0, bb, R);  // (behind the records' requests, in front of the wait for them: the slice travels under it)
+    // ... which the instruction scheduler has to be TOLD: the block's address needs nothing but the chunk record, and left alone
+    // it sank all four loads behind the wait for the records, into the operand round -- 8 KB per work-group on top of the
+    // burst that round already is.  Nothing crosses this line, so the requests stand where they are written.
+    __builtin_amdgcn_sched_barrier(0);
 #endif
     bwd_load<S, PAD, !PAD>(cur, rq, P, C, PC, has_row, table, B, rowidx, d_output, R);
   } else {
@@ -1616,6 +1666,8 @@ static RealDims real_dims(const Dims& d) {
   R.c2n = 0;
   R.v4 = ((d.r[1] & 3) == 0 ? 1 : 0) | ((d.r[2] & 3) == 0 ? 2 : 0) | ((d.q[2] & 3) == 0 ? 4 : 0);  // (the launchers clear it
                                                                                          // when an array is not 16-byte aligned)
+  const TableDiv td = table_div((unsigned)d.p[1], (unsigned long long)d.num_tables * (unsigned long long)d.p[1]);
+  R.tmul = td.mul; R.tsh = td.sh;
   return R;
 }
 
@@ -1629,6 +1681,8 @@ static int spec_launch_fwd_v(const Plan& P, const CorePtrs& C, float* rows, floa
   }
   RealDims Rv = R;
   if ((((uintptr_t)C.c[0]) | ((uintptr_t)C.c[1]) | ((uintptr_t)C.c[2])) & 15) Rv.v4 = 0;
+  // (the grid IS P.max_chunks: the single-sub-chunk kernel zeroes `zout` with that stride -- zero_output(zout, nzero, P.max_chunks) --
+  //  so a launch with fewer work-groups would leave part of it unzeroed)
   hipLaunchKernelGGL((spec_fwd_kernel<S, MULTI, FUSE, PAD>), dim3(P.max_chunks), dim3(kThreads), lds, st, TTX_KHEAD_ARGS(P, C) P, C, rows, zout, nzero,
                      F, Rv);
   TTX_HIP(hipGetLastError());
