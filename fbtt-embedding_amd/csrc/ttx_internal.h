@@ -203,6 +203,11 @@ struct DedupMap {
   int* occ_off;
 };
 constexpr int kDedupMaxN = 16384;  // one work-group sorts the batch in LDS
+#ifdef TTX_TEST_HOOKS  // (ttx_debug_dd_route: what this route's host code chose, for the tests -- include/ttx_test_hooks.h; defined beside the knobs' setters, ttx_tt.hip)
+#define TTX_DD_ROUTE(k, v) (ttx_debug_dd_route[k] = (int)(v))
+#else
+#define TTX_DD_ROUTE(k, v) ((void)0)
+#endif
 // header of the map: int [0] = distinct pairs; from byte 64 on, int64 tstart[tables + 1] = first pair of every table (the pairs
 // are table-major; written for 1 < tables <= dedup_max_tables(), the "offsets" the plan of the pairs groups its tables by)
 __host__ __device__ inline int64_t* dedup_tstart(const DedupMap& M) { return (int64_t*)((char*)M.nu + 64); }

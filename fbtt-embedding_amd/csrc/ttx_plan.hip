@@ -1658,8 +1658,9 @@ int plan_build_batches(const Dims& d, int nbatch, long long nnz, const int* n_de
 // One work-group sorts the batch's (table, index) keys -- 32 bits, stable LSD radix sort in LDS, the same wave
 // ranking as plan_small_kernel -- so that equal pairs end up adjacent with their occurrences in index order;
 // run heads are the distinct pairs.  Deterministic (no ordering-dependent atomics), one launch, <= 16384 lookups
-// (144 KB of LDS); larger batches and key spaces beyond 2^32 are not deduplicated (same results either way:
-// sharing the contraction of duplicates never changes a value, only how often it is computed).
+// (144 KB of LDS) of a key space of at most 2^32.  Larger batches, and key spaces up to 2^61, take the multi-work-group
+// sort of 64-bit keys further down (dedup_build_large): the same map, array for array.  (Sharing the contraction of
+// duplicates never changes a forward value, only how often it is computed.)
 // (batches beyond the single-work-group map also keep the key sort's buffers here: keys, values, the sort's workspace,
 //  run heads per block of 1024 sorted positions)
 // header: [0] distinct pairs, then (8-byte aligned, from int 16 on) tstart[kDedupMaxTables + 1]: first pair of every table
@@ -1952,8 +1953,9 @@ static int dedup_build_large(const Dims& d, long long nnz, const int64_t* indice
   char* sws = extra + 2 * align_up((size_t)nnz * 8);
   int* blk = (int*)(sws + align_up(sort_pairs_ws_bytes(nnz)));
   const int nblk = (int)dedup_blocks(nnz);
+  TTX_DD_ROUTE(TTX_DD_FORM, TTX_DD_LARGE), TTX_DD_ROUTE(TTX_DD_BPW, 0), TTX_DD_ROUTE(TTX_DD_PASSES, passes), TTX_DD_ROUTE(TTX_DD_NBLK, nblk);
   ProfScope ps(TTX_PROF_PLAN, stream);
-  hipLaunchKernelGGL(dd_keys_kernel, dim3(nblk), dim3(kDdThreads), 0, stream, N, E, d.num_tables, indices, tableidx, keys, vals);
+  hipLaunchKernelGGL(dd_keys_kernel,dim3(nblk), dim3(kDdThreads), 0, stream, N, E, d.num_tables, indices, tableidx, keys, vals);
   int64_t *sk = nullptr, *sv = nullptr;
   const int rc = sort_pairs_desc(nnz, keys, vals, sws, &sk, &sv, stream, passes);
   if (rc) return rc;
@@ -2001,7 +2003,9 @@ int dedup_build(const Dims& d, long long nnz, const int64_t* indices, const int6
                 hipStream_t stream) {
   const int rc = dedup_build_map(d, nnz, indices, tableidx, M, stream);
   if (rc) return rc;
+  TTX_DD_ROUTE(TTX_DD_TSTART, 0);
   if (d.num_tables <= kDedupMaxTables && plan_groups_tables(d, nnz)) {
+    TTX_DD_ROUTE(TTX_DD_TSTART, 1);
     ProfScope ps(TTX_PROF_PLAN, stream);
     hipLaunchKernelGGL(dedup_tstart_kernel, dim3((d.num_tables + 256) / 256), dim3(256), 0, stream, d.num_tables, M);
     TTX_HIP(hipGetLastError());
@@ -2022,11 +2026,13 @@ static int dedup_build_map(const Dims& d, long long nnz, const int64_t* indices,
   const size_t lds = (256 * kPlanWaves + 32 + 2 * (((size_t)N + 63) / 64 * 64)) * sizeof(int);
   const int per = ((N + kPlanWaves - 1) / kPlanWaves + kWave - 1) / kWave * kWave;
   const int nb = per / kWave;
+  TTX_DD_ROUTE(TTX_DD_FORM, TTX_DD_SMALL), TTX_DD_ROUTE(TTX_DD_PASSES, passes), TTX_DD_ROUTE(TTX_DD_NBLK, 0);
   ProfScope ps(TTX_PROF_PLAN, stream);
-#define TTX_DEDUP_LAUNCH(BPW)                                                                                 \
+#define TTX_DEDUP_LAUNCH(BPW)                                                                                \
   do {                                                                                                        \
     const int rc_attr = allow_dynamic_lds((const void*)dedup_small_kernel<BPW>, 160 * 1024);                  \
     if (rc_attr) return rc_attr;                                                                              \
+    TTX_DD_ROUTE(TTX_DD_BPW, BPW);                                                                            \
     hipLaunchKernelGGL(dedup_small_kernel<BPW>, dim3(1), dim3(kPlanThreads), lds, stream, N, E, d.num_tables, \
                        passes, indices, tableidx, M);                                                         \
   } while (0)

@@ -2447,6 +2447,7 @@ extern "C" {
 
 #ifdef TTX_TEST_HOOKS  // ---- the knobs' setters: libttx_hooks.so only (include/ttx_test_hooks.h) ----
 int ttx_debug_t4_route[TTX_T4_ROUTE_INTS] = {0};  // what the four-core route's host code chose last (TTX_T4_ROUTE)
+int ttx_debug_dd_route[TTX_DD_ROUTE_INTS] = {0};  // what the duplicate route's host code chose last (TTX_DD_ROUTE, ttx_internal.h)
 int ttx_debug_reduce_route = 0;  // the kernel the last reduce + apply launch was (TTX_REDUCE_FULL / TTX_REDUCE_SMALL; tt_backward_impl writes it)
 // debug: device buffer of 16 int64 stamps per work-group (NULL = off), scripts/phase_times.py
 int ttx_debug_stamps(void* device_buffer) {
@@ -3111,6 +3112,11 @@ int ttx_tt_forward_dd(const ttx_geom* g, int32_t B, int32_t D, int64_t nnz, cons
   if (rc) return rc;
   ProfScope ps(TTX_PROF_POOL, st);
   const int blocks = ((int)nnz + kThreads / 16 - 1) / (kThreads / 16);
+#ifdef TTX_TEST_HOOKS  // (ttx_debug_dd_route: the conditions of the dispatch below, word for word -- tests/test_dedup_routes_cpu.py holds the two texts together)
+  if (d.D % 4 == 0 && (((uintptr_t)rows | (uintptr_t)output) & 15) == 0 && nnz > kPoolSpanMin) TTX_DD_ROUTE(TTX_DD_POOL, TTX_DD_POOL_SPAN);
+  else if (d.D % 4 == 0 && (((uintptr_t)rows | (uintptr_t)output) & 15) == 0) TTX_DD_ROUTE(TTX_DD_POOL, TTX_DD_POOL_GATHER_VEC4);
+  else TTX_DD_ROUTE(TTX_DD_POOL, TTX_DD_POOL_GATHER_SCALAR);
+#endif
   if (d.D % 4 == 0 && (((uintptr_t)rows | (uintptr_t)output) & 15) == 0 && nnz > kPoolSpanMin)
     hipLaunchKernelGGL(pool_gather4_kernel, dim3(((int)nnz + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (int)nnz, B, d.D / 4,
                        rowidx, tableidx, M.uid, (const float4*)rows, psw, (float4*)output);
@@ -3142,10 +3148,12 @@ static int gsum_launch_t(const DedupMap& M, int N, int B, int D, const int64_t* 
                          const float* d_output, float* Gu, float* Pp, hipStream_t st, long long skip_key) {
   const int blocks = ((N + kGsSlice - 1) / kGsSlice + kGsThreads / 16 - 1) / (kGsThreads / 16);
   if (D % 4 == 0 && ((((uintptr_t)d_output) | ((uintptr_t)Gu)) & 15) == 0) {
+    TTX_DD_ROUTE(TTX_DD_GSUM, TTX_DD_VEC4);
     hipLaunchKernelGGL((gsum_slice_kernel<float4, kSkip>), dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D / 4, rowidx, tableidx, psw,
                        (const float4*)d_output, (float4*)Gu, (float4*)Pp, skip_key);
     hipLaunchKernelGGL(gsum_fold_kernel<float4>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, D / 4, (const float4*)Pp, (float4*)Gu);
   } else {
+    TTX_DD_ROUTE(TTX_DD_GSUM, TTX_DD_SCALAR);
     hipLaunchKernelGGL((gsum_slice_kernel<float, kSkip>), dim3(blocks), dim3(kGsThreads), 0, st, M, N, B, D, rowidx, tableidx, psw, d_output,
                        Gu, Pp, skip_key);
     hipLaunchKernelGGL(gsum_fold_kernel<float>, dim3(blocks), dim3(kGsThreads), 0, st, M, N, D, (const float*)Pp, Gu);

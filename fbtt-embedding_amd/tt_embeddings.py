@@ -422,7 +422,8 @@ def make_plan(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, nnz, indices, tabl
         return Plan(buf, nnz, (num_tables, tuple(tt_p_shapes), tuple(tt_q_shapes), tuple(tt_ranks)))
     if dedup:
         db = L.ttx_dedup_bytes(C.byref(g), nnz)
-        if db:  # (0: more than 16384 lookups or a key space beyond 2^32 -- the plain plan gives the same results)
+        if db:  # (0: tables of different row factors, or tables * prod(p) beyond 2^61 -- the plain plan gives the same results;
+            #  batches of any size and key spaces beyond 2^32 ARE mapped: csrc/ttx_plan.hip dedup_build_large)
             nb = L.ttx_plan_bytes(C.byref(g), nnz)
             buf = torch.empty(nb, dtype=torch.uint8, device=dev)
             dd = torch.empty(db, dtype=torch.uint8, device=dev)
@@ -1731,6 +1732,24 @@ def debug_t4_route(clear: bool = False) -> dict:
     out = dict(zip(T4_ROUTE_FIELDS, (int(x) for x in rec)))
     if clear:
         rec[:] = [0] * len(T4_ROUTE_FIELDS)
+    return out
+
+
+DD_ROUTE_FIELDS = ("form", "bpw", "passes", "nblk", "tstart", "pool", "gsum")
+
+
+def debug_dd_route(clear: bool = False) -> dict:
+    """Test helper (ttx_debug_dd_route, a global of the TEST library): what the host code of the duplicate-lookup route chose last
+    (include/ttx_test_hooks.h TTX_DD_*; zeros: none yet) -- the map's form, template argument, passes and blocks and whether
+    tstart was written (ttx_dedup_build), the pooling kernel (ttx_tt_forward_dd), the pre-sum's vector type (ttx_tt_backward_dd).
+    Run the calls inside `with test_library():`.  clear: zero the record after reading it."""
+    if _hooks is None:
+        hooks_lib()
+        _knobs_changed()
+    rec = (C.c_int * len(DD_ROUTE_FIELDS)).in_dll(_hooks, "ttx_debug_dd_route")
+    out = dict(zip(DD_ROUTE_FIELDS, (int(x) for x in rec)))
+    if clear:
+        rec[:] = [0] * len(DD_ROUTE_FIELDS)
     return out
 
 

@@ -57,6 +57,27 @@ extern int ttx_debug_reduce_route;
 #define TTX_T4_HELPER_VALU16 4
 #define TTX_T4_HELPER_VALU32 5
 extern int ttx_debug_t4_route[TTX_T4_ROUTE_INTS];
+/* What the host code of the duplicate-lookup route (csrc/ttx_plan.hip dedup_build / dedup_build_map / dedup_build_large,
+ * csrc/ttx_tt.hip ttx_tt_forward_dd / gsum_launch_t) chose LAST in this process (a plain global of the test library; zeros:
+ * none yet; tests/dedup_ref.py::route is the host mirror the tests compare it with).  The first five fields are written by
+ * ttx_dedup_build, TTX_DD_POOL by ttx_tt_forward_dd, TTX_DD_GSUM by the gradient pre-sum of ttx_tt_backward_dd (and of the
+ * sorted cache-row update, which launches the same two kernels). */
+#define TTX_DD_FORM 0         /* TTX_DD_SMALL = dedup_small_kernel, TTX_DD_LARGE = the 64-bit key sort (dedup_build_large) */
+#define TTX_DD_BPW 1          /* template argument of dedup_small_kernel (2, 4, 8, 12, 16); 0 for the large form */
+#define TTX_DD_PASSES 2       /* 8-bit passes of the sort */
+#define TTX_DD_NBLK 3         /* blocks of 1024 sorted positions of the large form (dd_count / dd_scan / dd_emit); 0 for the small form */
+#define TTX_DD_TSTART 4       /* 1 = dedup_tstart_kernel was launched */
+#define TTX_DD_POOL 5         /* TTX_DD_POOL_* */
+#define TTX_DD_GSUM 6         /* TTX_DD_VEC4 = gsum_slice_kernel / gsum_fold_kernel<float4>, TTX_DD_SCALAR = <float> */
+#define TTX_DD_ROUTE_INTS 7
+#define TTX_DD_SMALL 1
+#define TTX_DD_LARGE 2
+#define TTX_DD_POOL_GATHER_VEC4 1   /* pool_gather_kernel<float4> */
+#define TTX_DD_POOL_GATHER_SCALAR 2 /* pool_gather_kernel<float> */
+#define TTX_DD_POOL_SPAN 3          /* pool_gather4_kernel */
+#define TTX_DD_VEC4 1
+#define TTX_DD_SCALAR 2
+extern int ttx_debug_dd_route[TTX_DD_ROUTE_INTS];
 /* A/B knob (scripts/bench_cache.py): 1 = ttx_cache_forward uses the one-group-per-lookup kernel for every D */
 int ttx_debug_cache_fwd(int32_t lookup_groups);
 /* (scripts/phase_times.py) device buffer receiving 16 int64 wall-clock stamps per backward work-group; NULL = off */

@@ -83,7 +83,7 @@ def test_product_library_has_no_test_knobs():
     set -- and the library exports its C ABI only.  They live in libttx_hooks.so, the same sources with -DTTX_TEST_HOOKS
     (include/ttx_test_hooks.h), which the shim loads on the first use of a knob and leaves as soon as every knob is back at
     its default.  The same holds for the globals the test library's host code writes for the tests to read
-    (ttx_debug_reduce_route, ttx_debug_t4_route)."""
+    (ttx_debug_reduce_route, ttx_debug_t4_route, ttx_debug_dd_route)."""
     import subprocess
 
     import tt_embeddings as E
@@ -94,7 +94,7 @@ def test_product_library_has_no_test_knobs():
                           "ttx_debug_plan_layout", "ttx_debug_plan_route"}  # (the last two change nothing: how the plan tests see a plan)
     # ... and the globals the host code writes for the tests to read (what ran: neither changes what the library does)
     records = sorted(set(re.findall(r"\bextern\s+int\s+(ttx_[a-z0-9_]+)", hooks_hdr)))
-    assert records == ["ttx_debug_reduce_route", "ttx_debug_t4_route"]
+    assert records == ["ttx_debug_dd_route", "ttx_debug_reduce_route", "ttx_debug_t4_route"]
     so = os.path.join(ROOT, "fbtt-embedding_amd", "libttx.so")
     exported = [ln.split()[-1] for ln in subprocess.check_output(["nm", "-D", "--defined-only", so], text=True).splitlines()]
     assert exported and all(sym.startswith("ttx_") for sym in exported), [x for x in exported if not x.startswith("ttx_")]
@@ -105,6 +105,7 @@ def test_product_library_has_no_test_knobs():
     hooks = ctypes.CDLL(os.path.join(ROOT, "fbtt-embedding_amd", "libttx_hooks.so"))
     assert hooks.ttx_has_test_hooks() == 1 and all(hasattr(hooks, k) for k in knobs + records)
     assert set(E.debug_t4_route()) == set(E.T4_ROUTE_FIELDS) and E.lib() is E._product
+    assert set(E.debug_dd_route()) == set(E.DD_ROUTE_FIELDS) and E.lib() is E._product
     # the shim: product library until a knob moves, back when it is reset
     assert E.lib() is E._product and E.lib().ttx_has_test_hooks() == 0
     E.debug_skip(256)
