@@ -2,13 +2,16 @@
 """Compress a dense table, freeze it for serving in bf16, serve a batch:
 
     python examples/serve_bf16.py            # on cuda:0
+    python examples/serve_bf16.py --wide     # TT ranks 96: the column-blocked bf16 kernel (route "bf16w")
 
 1. a dense table (low TT rank plus noise) stands in for a trained nn.EmbeddingBag;
 2. `TTEmbeddingBag.from_pretrained` factors it by TT-SVD into an ordinary module;
 3. `TTInferenceBag.from_module` freezes that module: the cores rounded once to bf16, no Parameters, forward only -- the lookups
    run on the bf16 MFMA with fp32 accumulation (`served.route == "bf16"`; a geometry the kernel does not take says "fp32" and
-   serves the same rounded weights through the fp32 kernels);
+   serves the same rounded weights through the fp32 kernels; `from_module(trained, wide=True)` opts in to the column-blocked
+   bf16 kernel for ranks up to 128 and wide q1: `served.route == "bf16w"`);
 4. a batch is served and compared with the fp32 module and with the dense table."""
+import argparse
 import os
 import sys
 
@@ -20,6 +23,9 @@ sys.path.insert(0, os.path.join(ROOT, "fbtt-embedding_amd"))
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--wide", action="store_true", help="factor at TT ranks 96 and serve on the column-blocked bf16 kernel")
+    wide = ap.parse_args().wide
     import tt_embeddings_ops as ops
     import ttx_infer
     import ttx_svd
@@ -33,8 +39,8 @@ def main():
     weight += torch.randn_like(weight) * (0.02 * weight.norm() / weight.numel() ** 0.5)
     bag = nn.EmbeddingBag.from_pretrained(weight, freeze=True, mode="sum", include_last_offset=True)
 
-    trained = ops.TTEmbeddingBag.from_pretrained(weight, [16, 16], p, q, device=dev, use_cache=False)
-    served = ttx_infer.TTInferenceBag.from_module(trained)
+    trained = ops.TTEmbeddingBag.from_pretrained(weight, [96, 96] if wide else [16, 16], p, q, device=dev, use_cache=False)
+    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide)
     print(served)
     print(f"route {served.route}; parameters {len(list(served.parameters()))}; "
           f"buffers {sum(b.numel() * b.element_size() for b in served.buffers()) / 1e3:.0f} kB "

@@ -221,6 +221,13 @@ def _load(path):
     L.ttx_tt_rows_bf16_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_rows_bf16_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_rows_bf16.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_tt_rows_bf16w_supported.argtypes = [G]
+    L.ttx_tt_pack_bf16w_elems.restype = i64
+    L.ttx_tt_pack_bf16w_elems.argtypes = [G, i32]
+    L.ttx_tt_pack_bf16w.argtypes = [G, i32, vp, vp, vp]
+    L.ttx_tt_rows_bf16w_workspace_bytes.restype = C.c_size_t
+    L.ttx_tt_rows_bf16w_workspace_bytes.argtypes = [G, i32, i64]
+    L.ttx_tt_rows_bf16w.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
     return L
 
@@ -1130,49 +1137,79 @@ def tt_rows_bf16_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bo
     return bool(lib().ttx_tt_rows_bf16_supported(C.byref(g)))
 
 
-def pack_cores_bf16(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
-    """the fp32 cores rounded to bf16 (nearest even, as tensor.to(torch.bfloat16)) in the packed layout of the bf16 rows
-    kernel: one flat bfloat16 tensor per core."""
+def tt_rows_bf16w_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the column-blocked bf16 rows kernel take this geometry (T = 3, ranks <= 128, q0 <= 16, q1 <= 64, q2 <= 8)?
+    Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_rows_bf16w_supported(C.byref(g)))
+
+
+def _pack_cores_bf(kind, num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """kind: "bf16" (the narrow kernel's entry points) or "bf16w" (the column-blocked kernel's)"""
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
     dev = _dev(tt_cores[0])
     cores = _cores(tt_cores, g)
     lb = lib()
+    elems, pack = getattr(lb, f"ttx_tt_pack_{kind}_elems"), getattr(lb, f"ttx_tt_pack_{kind}")
     out = []
     with _guard(dev):
         for t, c in enumerate(cores):
-            n = lb.ttx_tt_pack_bf16_elems(C.byref(g), t)
+            n = elems(C.byref(g), t)
             if n <= 0:
-                raise RuntimeError("tt_embeddings: pack_cores_bf16: the bf16 kernel does not take this geometry "
-                                   "(tt_rows_bf16_supported)")
+                raise RuntimeError(f"tt_embeddings: pack_cores_{kind}: the {kind} kernel does not take this geometry "
+                                   f"(tt_rows_{kind}_supported)")
             pk = torch.empty(n, dtype=torch.bfloat16, device=dev)
-            _check(lb.ttx_tt_pack_bf16(C.byref(g), t, c.data_ptr(), pk.data_ptr(), _stream(dev)))
+            _check(pack(C.byref(g), t, c.data_ptr(), pk.data_ptr(), _stream(dev)))
             out.append(pk)
     return out
+
+
+def _tt_rows_bf(kind, num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan) -> torch.Tensor:
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(packed_cores[0])
+    if len(packed_cores) != 3 or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
+        raise RuntimeError(f"tt_embeddings: tt_rows_{kind} needs the three packed bfloat16 cores of pack_cores_{kind} on one device")
+    lb = lib()
+    elems = getattr(lb, f"ttx_tt_pack_{kind}_elems")
+    for t, c in enumerate(packed_cores):
+        if c.numel() != elems(C.byref(g), t):
+            raise RuntimeError(f"tt_embeddings: packed core {t} holds {c.numel()} elements, the geometry needs "
+                               f"{elems(C.byref(g), t)}")
+    indices = _i64(indices, "indices")
+    nnz = indices.numel()
+    rows = torch.empty((nnz, D), dtype=torch.float32, device=dev)
+    st = _stream(dev)
+    ws = _workspace(dev, st, 0 if plan is not None else getattr(lb, f"ttx_tt_rows_{kind}_workspace_bytes")(C.byref(g), D, nnz))
+    with _guard(dev):
+        _check(getattr(lb, f"ttx_tt_rows_{kind}")(C.byref(g), D, nnz, indices.data_ptr(),
+                                                  None if tableidx is None else _i64(tableidx, "tableidx").data_ptr(),
+                                                  _ptr_array(packed_cores), rows.data_ptr(), _plan_ptr(plan, nnz), ws.data_ptr(),
+                                                  ws.numel(), st))
+    return rows
+
+
+def pack_cores_bf16(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """the fp32 cores rounded to bf16 (nearest even, as tensor.to(torch.bfloat16)) in the packed layout of the bf16 rows
+    kernel: one flat bfloat16 tensor per core."""
+    return _pack_cores_bf("bf16", num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores)
 
 
 def tt_rows_bf16(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores,
                  plan: Optional[Plan] = None) -> torch.Tensor:
     """rows [nnz, D] float32 in lookup order from the packed bf16 cores of pack_cores_bf16; `plan`: the batch's plan
     (make_plan / lookup_prologue), None: built in the workspace."""
-    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
-    dev = _dev(packed_cores[0])
-    if len(packed_cores) != 3 or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
-        raise RuntimeError("tt_embeddings: tt_rows_bf16 needs the three packed bfloat16 cores of pack_cores_bf16 on one device")
-    lb = lib()
-    for t, c in enumerate(packed_cores):
-        if c.numel() != lb.ttx_tt_pack_bf16_elems(C.byref(g), t):
-            raise RuntimeError(f"tt_embeddings: packed core {t} holds {c.numel()} elements, the geometry needs "
-                               f"{lb.ttx_tt_pack_bf16_elems(C.byref(g), t)}")
-    indices = _i64(indices, "indices")
-    nnz = indices.numel()
-    rows = torch.empty((nnz, D), dtype=torch.float32, device=dev)
-    st = _stream(dev)
-    ws = _workspace(dev, st, 0 if plan is not None else lb.ttx_tt_rows_bf16_workspace_bytes(C.byref(g), D, nnz))
-    with _guard(dev):
-        _check(lb.ttx_tt_rows_bf16(C.byref(g), D, nnz, indices.data_ptr(),
-                                   None if tableidx is None else _i64(tableidx, "tableidx").data_ptr(), _ptr_array(packed_cores),
-                                   rows.data_ptr(), _plan_ptr(plan, nnz), ws.data_ptr(), ws.numel(), st))
-    return rows
+    return _tt_rows_bf("bf16", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
+
+
+def pack_cores_bf16w(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """pack_cores_bf16 for the geometries of the column-blocked kernel (tt_rows_bf16w_supported): the same packed layout"""
+    return _pack_cores_bf("bf16w", num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores)
+
+
+def tt_rows_bf16w(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores,
+                  plan: Optional[Plan] = None) -> torch.Tensor:
+    """tt_rows_bf16 on the column-blocked kernel (ranks up to 128, any q1 <= 64) from the cores of pack_cores_bf16w"""
+    return _tt_rows_bf("bf16w", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
 
 
 def bag_sum_pool(rows: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:

@@ -11,6 +11,10 @@ larger ranks) the module keeps the SAME rounded weights as float32 in the ordina
 source, and calls the existing fp32 forward: the call always works, with the same rounding of the weights.  On CPU tensors the
 bf16 route computes the same chain product with torch ops from the packed cores (what the tests run without a GPU).
 
+`from_module(trained, wide=True)` opts in to the column-blocked kernel for the three-core geometries the narrow
+one refuses -- ranks up to 128, any q1 <= 64: `route == "bf16w"`, the same packed buffers, `tt_rows_bf16w` in place of
+`tt_rows_bf16`.  Every other geometry keeps the route it has without the flag.
+
 Limits: no fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, no live row
 cache, not the mixed-cardinality or sharded module classes (the C entry points do take p_tables geometries); nothing trains."""
 from typing import List, Optional, Sequence
@@ -71,7 +75,7 @@ class TTInferenceBag(nn.Module):
         self.route = "bf16"
 
     @classmethod
-    def from_module(cls, module: nn.Module) -> "TTInferenceBag":
+    def from_module(cls, module: nn.Module, wide: bool = False) -> "TTInferenceBag":
         if not isinstance(module, _ops.TableBatchedTTEmbeddingBag) or isinstance(module.tt_p_shapes[0], (list, tuple)) \
                 or hasattr(module, "_p_flat"):
             raise TypeError("TTInferenceBag.from_module takes a TTEmbeddingBag, a TableBatchedTTEmbeddingBag or a TTEmbedding, got "
@@ -93,10 +97,17 @@ class TTInferenceBag(nn.Module):
         self.tt_ranks = list(module.tt_ranks)
         self.mode, self.include_last_offset = mode, bool(module.include_last_offset)
         cores = [c.detach() for c in module.tt_cores]
-        if _engine.tt_rows_bf16_supported(self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks):
+        geom = (self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks)
+        if _engine.tt_rows_bf16_supported(*geom):
             self.route = "bf16"
+        elif wide and _engine.tt_rows_bf16w_supported(*geom):
+            self.route = "bf16w"  # (opt-in: the column-blocked kernel where the narrow one refuses)
+        else:
+            self.route = "fp32"
+        if self.route != "fp32":
             if cores[0].is_cuda:
-                packed = _engine.pack_cores_bf16(self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, cores)
+                pack = _engine.pack_cores_bf16 if self.route == "bf16" else _engine.pack_cores_bf16w
+                packed = pack(*geom, cores)
             else:
                 packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks)
             for t, pk in enumerate(packed):
@@ -104,7 +115,6 @@ class TTInferenceBag(nn.Module):
         else:
             # the same rounding of the weights on the fp32 kernels: a twin of the source built by its own constructor (no
             # cache, no optimizer state) whose cores are BUFFERS holding the bf16 values as float32
-            self.route = "fp32"
             kw = module._ctor_kwargs()
             kw.update(use_cache=False, sparse=False, optimizer=_ops.OptimType.SGD, dedup=False, weight_dist="uniform")
             kw.pop("cache_size", None), kw.pop("hashtbl_size", None)
@@ -122,7 +132,12 @@ class TTInferenceBag(nn.Module):
     def _packed(self) -> List[torch.Tensor]:
         return [self.packed_core0, self.packed_core1, self.packed_core2]
 
-    # ------------------------------------------------------------------ rows of the bf16 route
+    # ------------------------------------------------------------------ rows of the bf16 routes
+    def _rows_hip(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor], plan=None) -> torch.Tensor:
+        rows = _engine.tt_rows_bf16 if self.route == "bf16" else _engine.tt_rows_bf16w
+        n = 1 if tableidx is None else self.num_tables
+        return rows(n, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, tableidx, self._packed(), plan)
+
     def _rows_torch(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor]) -> torch.Tensor:
         """CPU tensors (any device, really): the chain product in float32 from the packed cores"""
         c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks)
@@ -169,7 +184,7 @@ class TTInferenceBag(nn.Module):
             if flat.numel() == 0:
                 return torch.zeros(tuple(indices.shape) + (D,), dtype=torch.float32, device=indices.device)
             if flat.is_cuda:
-                rows = _engine.tt_rows_bf16(1, D, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, None, self._packed())
+                rows = self._rows_hip(flat, None)
             else:
                 rows = self._rows_torch(flat, None)
             return rows.view(tuple(indices.shape) + (D,))
@@ -184,8 +199,7 @@ class TTInferenceBag(nn.Module):
         if flat.is_cuda:
             _, tableidx, plan = _engine.lookup_prologue(flat, offsets, self.num_tables, self.tt_p_shapes, self.tt_q_shapes,
                                                         self.tt_ranks)
-            rows = _engine.tt_rows_bf16(self.num_tables, D, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, tableidx,
-                                        self._packed(), plan)
+            rows = self._rows_hip(flat, tableidx, plan)
             out = _engine.bag_sum_pool(rows, offsets)
             if self.mode == "mean":
                 out = _engine.bag_mean_scale(out, offsets)

@@ -933,6 +933,31 @@ int ttx_tt_rows_bf16(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* i
                      ttx_stream_t stream);
 int ttx_bag_sum_pool(int64_t nb, int32_t D, const int64_t* offsets, const float* rows, float* output, ttx_stream_t stream);
 
+/* ---- bf16 inference forward, column-blocked (csrc/ttx_tt_bf16w.hip; not in the reference) -----------------
+ * The same forward for the shapes the kernel above refuses: ranks up to 128 and any q1 <= 64.  OPT-IN: a surface of its own;
+ * the five entry points above return exactly what they returned before it existed.
+ * SUPPORTED (ttx_tt_rows_bf16w_supported: host-side, stateless, touches no device; any p, any num_tables, p_tables or not):
+ *   T == 3, r1 <= 128 and r2 <= 128, q0 <= 16, q1 <= 64, q2 <= 8 -- a superset of the narrow kernel's shapes.  Everything else
+ *   returns 0 here and TTX_EUNSUPPORTED from the pack and rows calls.
+ * PACKED LAYOUT: the one above, for any rank of this domain (ttx_tt_pack_bf16w_elems / ttx_tt_pack_bf16w: the same sizes, the
+ *   same rounding, bit for bit; where both kernels take a geometry the two packs write the same bytes).
+ * ROWS  ttx_tt_rows_bf16w: arguments, plan, workspace (ttx_tt_rows_bf16w_workspace_bytes), output order, determinism and capture
+ *   as ttx_tt_rows_bf16.  One work-group of 256 threads per pivot chunk; a pass of 64 rows (lookup, a) keeps its core-0
+ *   fragments in registers and walks the q1 blocks, x_0 of ONE block at a time in one of two alternating LDS tiles
+ *   [64][16 ceil(r2 / 16) + 4] fp32 (r2 = 128: 2 x 33 KiB); the last core is contracted from the fp32 x_0 by four lanes per
+ *   (lookup, a), each a quarter of k2, summed across the quad in a fixed order.  The pass's core-2 slices are staged in LDS where
+ *   the work-group stays within 80 KiB, read from memory otherwise.
+ * NUMERICS: the bound above (its fp32 term holds for any order of summation; x_0 is not rounded: the first term stays unused,
+ *   cores of small integers give exact rows).
+ * ERRORS: as above, under the names pack_bf16w / tt_rows_bf16w in ttx_last_error(). */
+int ttx_tt_rows_bf16w_supported(const ttx_geom* g);
+int64_t ttx_tt_pack_bf16w_elems(const ttx_geom* g, int32_t t);
+int ttx_tt_pack_bf16w(const ttx_geom* g, int32_t t, const float* core_f32, void* packed, ttx_stream_t stream);
+size_t ttx_tt_rows_bf16w_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz);
+int ttx_tt_rows_bf16w(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                      const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                      ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
