@@ -3,13 +3,15 @@
 
     python examples/serve_bf16.py            # on cuda:0
     python examples/serve_bf16.py --wide     # TT ranks 96: the column-blocked bf16 kernel (route "bf16w")
+    python examples/serve_bf16.py --mfma-tail  # D = 1024, q = [8, 8, 16]: both products on the bf16 MFMA (route "bf16m")
 
 1. a dense table (low TT rank plus noise) stands in for a trained nn.EmbeddingBag;
 2. `TTEmbeddingBag.from_pretrained` factors it by TT-SVD into an ordinary module;
 3. `TTInferenceBag.from_module` freezes that module: the cores rounded once to bf16, no Parameters, forward only -- the lookups
    run on the bf16 MFMA with fp32 accumulation (`served.route == "bf16"`; a geometry the kernel does not take says "fp32" and
    serves the same rounded weights through the fp32 kernels; `from_module(trained, wide=True)` opts in to the column-blocked
-   bf16 kernel for ranks up to 128 and wide q1: `served.route == "bf16w"`);
+   bf16 kernel for ranks up to 128 and wide q1: `served.route == "bf16w"`; `from_module(trained, mfma_tail=True)` to the
+   kernel for a last factor q2 up to 32, the default factorings of widths from 640 up: `served.route == "bf16m"`);
 4. a batch is served and compared with the fp32 module and with the dense table."""
 import argparse
 import os
@@ -25,14 +27,16 @@ sys.path.insert(0, os.path.join(ROOT, "fbtt-embedding_amd"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wide", action="store_true", help="factor at TT ranks 96 and serve on the column-blocked bf16 kernel")
-    wide = ap.parse_args().wide
+    ap.add_argument("--mfma-tail", action="store_true", help="a table of width 1024 (q = [8, 8, 16]) served on the MFMA-tail bf16 kernel")
+    args = ap.parse_args()
+    wide, tail = args.wide, args.mfma_tail
     import tt_embeddings_ops as ops
     import ttx_infer
     import ttx_svd
 
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    E, D, p, q = 100_000, 64, [40, 50, 50], [4, 4, 4]
+    E, D, p, q = (5_000, 1024, [10, 20, 25], [8, 8, 16]) if tail else (100_000, 64, [40, 50, 50], [4, 4, 4])
     r = [1, 8, 8, 1]
     cores = [torch.randn(r[k], p[k], q[k], r[k + 1], device=dev) / r[k] ** 0.5 for k in range(3)]
     weight = ttx_svd.tt_full(cores, E)
@@ -40,7 +44,7 @@ def main():
     bag = nn.EmbeddingBag.from_pretrained(weight, freeze=True, mode="sum", include_last_offset=True)
 
     trained = ops.TTEmbeddingBag.from_pretrained(weight, [96, 96] if wide else [16, 16], p, q, device=dev, use_cache=False)
-    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide)
+    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide, mfma_tail=tail)
     print(served)
     print(f"route {served.route}; parameters {len(list(served.parameters()))}; "
           f"buffers {sum(b.numel() * b.element_size() for b in served.buffers()) / 1e3:.0f} kB "

@@ -228,6 +228,13 @@ def _load(path):
     L.ttx_tt_rows_bf16w_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_rows_bf16w_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_rows_bf16w.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_tt_rows_bf16m_supported.argtypes = [G]
+    L.ttx_tt_pack_bf16m_elems.restype = i64
+    L.ttx_tt_pack_bf16m_elems.argtypes = [G, i32]
+    L.ttx_tt_pack_bf16m.argtypes = [G, i32, vp, vp, vp]
+    L.ttx_tt_rows_bf16m_workspace_bytes.restype = C.c_size_t
+    L.ttx_tt_rows_bf16m_workspace_bytes.argtypes = [G, i32, i64]
+    L.ttx_tt_rows_bf16m.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
     return L
 
@@ -1144,8 +1151,15 @@ def tt_rows_bf16w_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> b
     return bool(lib().ttx_tt_rows_bf16w_supported(C.byref(g)))
 
 
+def tt_rows_bf16m_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the MFMA-tail bf16 rows kernel take this geometry (T = 3, ranks <= 128, q0 <= 16, q1 <= 64, q2 <= 32, the x_0 of one
+    lookup within a work-group's LDS)?  Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_rows_bf16m_supported(C.byref(g)))
+
+
 def _pack_cores_bf(kind, num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
-    """kind: "bf16" (the narrow kernel's entry points) or "bf16w" (the column-blocked kernel's)"""
+    """kind: "bf16" (the narrow kernel's entry points), "bf16w" (the column-blocked kernel's) or "bf16m" (the MFMA-tail kernel's)"""
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
     dev = _dev(tt_cores[0])
     cores = _cores(tt_cores, g)
@@ -1210,6 +1224,18 @@ def tt_rows_bf16w(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, ta
                   plan: Optional[Plan] = None) -> torch.Tensor:
     """tt_rows_bf16 on the column-blocked kernel (ranks up to 128, any q1 <= 64) from the cores of pack_cores_bf16w"""
     return _tt_rows_bf("bf16w", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
+
+
+def pack_cores_bf16m(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """pack_cores_bf16 for the MFMA-tail kernel (tt_rows_bf16m_supported): cores 0 and 1 in the same layout, core 2 transposed
+    ([Q2P][K2p], its k2 index contiguous)"""
+    return _pack_cores_bf("bf16m", num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores)
+
+
+def tt_rows_bf16m(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores,
+                  plan: Optional[Plan] = None) -> torch.Tensor:
+    """tt_rows_bf16 on the MFMA-tail kernel (q2 up to 32, both products on the bf16 MFMA) from the cores of pack_cores_bf16m"""
+    return _tt_rows_bf("bf16m", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
 
 
 def bag_sum_pool(rows: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:

@@ -15,6 +15,11 @@ bf16 route computes the same chain product with torch ops from the packed cores 
 one refuses -- ranks up to 128, any q1 <= 64: `route == "bf16w"`, the same packed buffers, `tt_rows_bf16w` in place of
 `tt_rows_bf16`.  Every other geometry keeps the route it has without the flag.
 
+`from_module(trained, mfma_tail=True)` opts in to the kernel that runs BOTH products on the bf16 MFMA for the
+geometries the two above refuse for their last factor -- q2 up to 32, the default factorings of every width from 640 up:
+`route == "bf16m"`, core 2 packed transposed, `tt_rows_bf16m`.  It rounds x_0 once to bf16: within the same bound, not bit-equal
+to the fp32 route.  Routes are tried in the order "bf16", "bf16w" (with `wide`), "bf16m" (with `mfma_tail`), "fp32".
+
 Limits: no fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, no live row
 cache, not the mixed-cardinality or sharded module classes (the C entry points do take p_tables geometries); nothing trains."""
 from typing import List, Optional, Sequence
@@ -30,24 +35,30 @@ def _pad_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
-def packed_shapes(q: Sequence[int], ranks: Sequence[int]):
-    """(per-slice shape of each packed core, the valid extents inside it) of a three-core geometry; ranks = [1, r1, r2, 1]"""
+def packed_shapes(q: Sequence[int], ranks: Sequence[int], mfma_tail: bool = False):
+    """(per-slice shape of each packed core, the valid extents inside it) of a three-core geometry; ranks = [1, r1, r2, 1];
+    mfma_tail: core 2 in the transposed layout of the MFMA-tail kernel, [Q2P = q2 up to 16][K2p = r2 up to 32]"""
     q0, q1, q2 = (int(x) for x in q)
     r1, r2 = int(ranks[1]), int(ranks[2])
     K1p, N1 = _pad_up(r1, 32), q1 * r2
-    return ([(q0, K1p), (_pad_up(N1, 16), K1p), (r2, 4 if q2 <= 4 else 8)], [(q0, r1), (N1, r1), (r2, q2)])
+    last = ((_pad_up(q2, 16), _pad_up(r2, 32)), (q2, r2)) if mfma_tail else ((r2, 4 if q2 <= 4 else 8), (r2, q2))
+    return ([(q0, K1p), (_pad_up(N1, 16), K1p), last[0]], [(q0, r1), (N1, r1), last[1]])
 
 
-def pack_cores_torch(cores: Sequence[torch.Tensor], q: Sequence[int], ranks: Sequence[int]) -> List[torch.Tensor]:
-    """the packed bf16 layout of include/ttx.h with torch ops (any device): what ttx_tt_pack_bf16 writes, bit for bit"""
-    full, valid = packed_shapes(q, ranks)
-    r1 = int(ranks[1])
+def pack_cores_torch(cores: Sequence[torch.Tensor], q: Sequence[int], ranks: Sequence[int],
+                     mfma_tail: bool = False) -> List[torch.Tensor]:
+    """the packed bf16 layout of include/ttx.h with torch ops (any device): what ttx_tt_pack_bf16 (mfma_tail:
+    ttx_tt_pack_bf16m) writes, bit for bit"""
+    full, valid = packed_shapes(q, ranks, mfma_tail)
+    r1, r2 = int(ranks[1]), int(ranks[2])
     out = []
     for t, c in enumerate(cores):
         c = c.detach().reshape(-1, c.size(-1))  # [slices, r q r']
         S = c.size(0)
         if t == 1:  # [r1][q1 r2] -> column-major: K contiguous per output column
             c = c.view(S, r1, -1).transpose(1, 2)
+        if t == 2 and mfma_tail:  # [r2][q2] -> [q2][r2]: K contiguous per output column
+            c = c.view(S, r2, -1).transpose(1, 2)
         c = c.reshape(S, *valid[t]).to(torch.bfloat16)
         pk = torch.zeros((S,) + full[t], dtype=torch.bfloat16, device=c.device)
         pk[:, :valid[t][0], :valid[t][1]] = c
@@ -55,13 +66,14 @@ def pack_cores_torch(cores: Sequence[torch.Tensor], q: Sequence[int], ranks: Seq
     return out
 
 
-def unpack_cores_torch(packed: Sequence[torch.Tensor], q: Sequence[int], ranks: Sequence[int]) -> List[torch.Tensor]:
+def unpack_cores_torch(packed: Sequence[torch.Tensor], q: Sequence[int], ranks: Sequence[int],
+                       mfma_tail: bool = False) -> List[torch.Tensor]:
     """-> float32 cores [slices, r q r'] in the ordinary layout, holding exactly the bf16 values"""
-    full, valid = packed_shapes(q, ranks)
+    full, valid = packed_shapes(q, ranks, mfma_tail)
     out = []
     for t, pk in enumerate(packed):
         c = pk.view(-1, *full[t])[:, :valid[t][0], :valid[t][1]].float()
-        if t == 1:
+        if t == 1 or (t == 2 and mfma_tail):
             c = c.transpose(1, 2)
         out.append(c.reshape(c.size(0), -1).contiguous())
     return out
@@ -75,7 +87,7 @@ class TTInferenceBag(nn.Module):
         self.route = "bf16"
 
     @classmethod
-    def from_module(cls, module: nn.Module, wide: bool = False) -> "TTInferenceBag":
+    def from_module(cls, module: nn.Module, wide: bool = False, mfma_tail: bool = False) -> "TTInferenceBag":
         if not isinstance(module, _ops.TableBatchedTTEmbeddingBag) or isinstance(module.tt_p_shapes[0], (list, tuple)) \
                 or hasattr(module, "_p_flat"):
             raise TypeError("TTInferenceBag.from_module takes a TTEmbeddingBag, a TableBatchedTTEmbeddingBag or a TTEmbedding, got "
@@ -102,14 +114,16 @@ class TTInferenceBag(nn.Module):
             self.route = "bf16"
         elif wide and _engine.tt_rows_bf16w_supported(*geom):
             self.route = "bf16w"  # (opt-in: the column-blocked kernel where the narrow one refuses)
+        elif mfma_tail and _engine.tt_rows_bf16m_supported(*geom):
+            self.route = "bf16m"  # (opt-in: both products on the MFMA, q2 up to 32)
         else:
             self.route = "fp32"
         if self.route != "fp32":
             if cores[0].is_cuda:
-                pack = _engine.pack_cores_bf16 if self.route == "bf16" else _engine.pack_cores_bf16w
-                packed = pack(*geom, cores)
+                pack = {"bf16": _engine.pack_cores_bf16, "bf16w": _engine.pack_cores_bf16w, "bf16m": _engine.pack_cores_bf16m}
+                packed = pack[self.route](*geom, cores)
             else:
-                packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks)
+                packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
             for t, pk in enumerate(packed):
                 self.register_buffer(f"packed_core{t}", pk)
         else:
@@ -134,13 +148,13 @@ class TTInferenceBag(nn.Module):
 
     # ------------------------------------------------------------------ rows of the bf16 routes
     def _rows_hip(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor], plan=None) -> torch.Tensor:
-        rows = _engine.tt_rows_bf16 if self.route == "bf16" else _engine.tt_rows_bf16w
+        rows = {"bf16": _engine.tt_rows_bf16, "bf16w": _engine.tt_rows_bf16w, "bf16m": _engine.tt_rows_bf16m}[self.route]
         n = 1 if tableidx is None else self.num_tables
         return rows(n, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, tableidx, self._packed(), plan)
 
     def _rows_torch(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor]) -> torch.Tensor:
         """CPU tensors (any device, really): the chain product in float32 from the packed cores"""
-        c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks)
+        c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
         p, q, (r1, r2) = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks[1:3]
         idx = flat.clamp(min=0)
         i2 = (idx % p[2]).clamp(max=p[2] - 1)

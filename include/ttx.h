@@ -958,6 +958,36 @@ int ttx_tt_rows_bf16w(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* 
                       const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
                       ttx_stream_t stream);
 
+/* ---- bf16 inference forward, MFMA tail (csrc/ttx_tt_bf16m.hip; not in the reference) ------------------------
+ * The same forward for the last factors the two kernels above refuse: q2 up to 32 (the default factorings of every embedding
+ * width from 640 up), with BOTH products on mfma_f32_16x16x32_bf16.  OPT-IN: a surface of its own; every entry point above
+ * returns exactly what it returned before it existed.
+ * SUPPORTED (ttx_tt_rows_bf16m_supported: host-side, stateless, touches no device; any p, any num_tables, p_tables or not):
+ *   T == 3, r1 <= 128 and r2 <= 128, q0 <= 16, q1 <= 64, q2 <= 32, and the bf16 x_0 of ONE lookup, q0 AS bytes with
+ *   K2p = r2 rounded up to 32, S = 2 (K2p + 8), AS = q1 S (+ 16 where q1 is even), plus 2 KiB of lookup records, within 160 KiB
+ *   of LDS (q0 q1 = 1024 at r2 = 128 does not fit).  Everything else returns 0 here and TTX_EUNSUPPORTED from the pack and rows
+ *   calls.
+ * PACKED LAYOUT: cores 0 and 1 as above ([q0][K1p], [N1p][K1p]), for any rank of this domain.  Core 2 is TRANSPOSED:
+ *   core 2   [slices][Q2P][K2p]    Q2P = q2 rounded up to 16, K2p = r2 rounded up to 32; column c of the fp32 slice [r2][q2] holds
+ *                                  its k2 index contiguously at c K2p + k2: the A fragment of row c is one 16-byte load; padding +0
+ *   ttx_tt_pack_bf16m_elems / ttx_tt_pack_bf16m: as above, the same rounding bit for bit.
+ * ROWS  ttx_tt_rows_bf16m: arguments, plan, workspace (ttx_tt_rows_bf16m_workspace_bytes), output order, determinism and capture
+ *   as ttx_tt_rows_bf16.  One work-group of 256 threads per pivot chunk; a pass of SC lookups (SC q0 <= 64 and the pass's x_0
+ *   within 80 KiB, at least one) computes x_0^T on the MFMA (M: core-1 columns, N: rows (lookup, a)), rounds it ONCE to bf16
+ *   (nearest even) into LDS, and after a barrier computes row^T per lookup on the MFMA (M: c, N: 16 rows (a, b), K: k2); a lane
+ *   stores four consecutive c of one row (a, b).
+ * NUMERICS: the bound above, its 2^-8 term IN USE (x_0 is rounded to bf16): rows are not bit-equal to the fp32 kernels' on the
+ *   same rounded cores.  Cores of integers in {-1, 0, 1} still give exact rows (|x_0| <= r1 <= 128 is exact in bf16,
+ *   |row| <= 16384 < 2^24).
+ * ERRORS: as above, under the names pack_bf16m / tt_rows_bf16m in ttx_last_error(). */
+int ttx_tt_rows_bf16m_supported(const ttx_geom* g);
+int64_t ttx_tt_pack_bf16m_elems(const ttx_geom* g, int32_t t);
+int ttx_tt_pack_bf16m(const ttx_geom* g, int32_t t, const float* core_f32, void* packed, ttx_stream_t stream);
+size_t ttx_tt_rows_bf16m_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz);
+int ttx_tt_rows_bf16m(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                      const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                      ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
