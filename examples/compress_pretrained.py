@@ -35,6 +35,11 @@ def main():
     def report(what, m):
         ranks, bound, norm = m.compression[0]
         err = (m.full_weight(0) - bag.weight.detach()).norm().item()
+        # the same figure slab by slab: dense_rows expands 2^16 rows at a time in one HIP kernel, the table is never formed whole
+        slab, sq = 1 << 16, 0.0
+        for s in range(0, E, slab):
+            sq += (m.dense_rows(s, min(E, s + slab)) - bag.weight.detach()[s:s + slab]).double().pow(2).sum().item()
+        assert abs(sq ** 0.5 - err) <= 1e-4 * err + 1e-6
         n_tt, n_dense = sum(c.numel() for c in m.tt_cores), bag.weight.numel()
         print(f"{what}: ranks {ranks}, ||W - TT|| / ||W|| = {err / norm:.4f} (the bound of its own factorisation: {bound / norm:.4f}), "
               f"{n_dense / n_tt:.0f}x fewer parameters")

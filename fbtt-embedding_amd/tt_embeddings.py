@@ -235,6 +235,8 @@ def _load(path):
     L.ttx_tt_rows_bf16m_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_rows_bf16m_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_rows_bf16m.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_tt_expand_supported.argtypes = [G]
+    L.ttx_tt_expand.argtypes = [G, i32, i64, i64, vp, vp, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
     return L
 
@@ -1236,6 +1238,35 @@ def tt_rows_bf16m(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, ta
                   plan: Optional[Plan] = None) -> torch.Tensor:
     """tt_rows_bf16 on the MFMA-tail kernel (q2 up to 32, both products on the bf16 MFMA) from the cores of pack_cores_bf16m"""
     return _tt_rows_bf("bf16m", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
+
+
+# ---- dense rows: a range of a table expanded (include/ttx.h "dense rows"; the method on top: dense_rows of the modules) ----
+def tt_expand_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the expand kernel take this geometry (T = 3, ranks <= 128, q0 <= 16, q1 <= 64, q2 <= 32, the x_0 of one (i0, i1)
+    prefix within a work-group's LDS)?  Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_expand_supported(C.byref(g)))
+
+
+def tt_expand(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, table, row_begin, row_end, tt_cores,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rows [row_end - row_begin, D] float32: the rows [row_begin, row_end) of table `table` from the fp32 cores, ONE launch, no
+    indices and no plan.  `out`: written in place (float32, contiguous, on the cores' device, of that shape) and returned."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(tt_cores[0])
+    cores = _cores(tt_cores, g)
+    n = int(row_end) - int(row_begin)
+    if D != g.q[0] * g.q[1] * (g.q[2] if g.T > 2 else 1) * (g.q[3] if g.T > 3 else 1):
+        raise RuntimeError(f"tt_embeddings: tt_expand: D={D} does not match prod(tt_q_shapes)")
+    if out is None:
+        out = torch.empty((max(n, 0), D), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or tuple(out.shape) != (n, D):
+        raise RuntimeError(f"tt_embeddings: tt_expand: out must be a contiguous float32 tensor of shape {(n, D)} on {dev}, got "
+                           f"{tuple(out.shape)} {out.dtype} on {out.device}")
+    with _guard(dev):
+        _check(lib().ttx_tt_expand(C.byref(g), int(table), int(row_begin), int(row_end), _ptr_array(cores),
+                                   out.data_ptr(), _stream(dev)))
+    return out
 
 
 def bag_sum_pool(rows: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:

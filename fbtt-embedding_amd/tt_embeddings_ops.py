@@ -971,11 +971,58 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     # ------------------------------------------------------------------ init
     def full_weight(self, table: Optional[int] = None) -> torch.Tensor:
         """`table` None: the one table of a one-table module expanded to [prod(tt_p_shapes), D] (the reference's).  An integer (not
-        in the reference): that table's [num_embeddings, D], of any number of tables."""
+        in the reference): that table's [num_embeddings, D], of any number of tables.  Torch ops that form the whole table;
+        `dense_rows` expands any range of rows in one HIP kernel."""
         if table is not None:
             return _svd.tt_full(self.table_cores(table), self.num_embeddings)
         assert self.num_tables == 1, "full_weight() only supported for num_tables == 1 for now"
         return tt_matrix_to_full(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, list(self.tt_cores), [1, 0, 2, 3])
+
+    # ------------------------------------------------- dense rows (DESIGN.md 4.22)
+    _DENSE_ROWS_BLOCK = 1 << 18  # rows per ttx_tt_rows call where the expand kernel does not take the geometry
+
+    def _table_view(self, k: int):
+        """-> (rows the module serves of table k, its own tt_p_shapes, its slices of the cores as views [1, p_t, slice])"""
+        return self.num_embeddings, list(self.tt_p_shapes), [c.detach()[k:k + 1] for c in self.tt_cores]
+
+    @torch.no_grad()
+    def dense_rows(self, start: int = 0, stop: Optional[int] = None, table: int = 0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rows [start, stop) of table `table` as a dense [stop - start, D] float32 tensor (`stop` None: num_embeddings); `out`:
+        written in place and returned.  On the GPU: ONE launch of the expand kernel (tt_embeddings.tt_expand: no indices, no
+        plan) where it takes the geometry, else ttx_tt_rows over blocks of consecutive indices; CPU cores: ttx_svd.tt_full."""
+        k = self._table_index(table)
+        E, p, one = self._table_view(k)
+        start, stop = int(start), E if stop is None else int(stop)
+        if not 0 <= start <= stop:
+            raise IndexError(f"dense_rows: [{start}, {stop}) is not a range of rows")
+        if stop > E:
+            raise IndexError(f"dense_rows: stop={stop} is beyond the table's {E} rows")
+        if self.use_cache and not self.warmup:
+            raise ValueError("dense_rows: the module's row cache is live -- its cached rows were trained away from the cores, "
+                             "and a copy of the cores would serve stale rows; fold them back with cache_populate(write_back=...) "
+                             "and reset_cache(), or freeze a fresh module")
+        cores = [c.detach() for c in self.tt_cores]
+        dev, D, n = cores[0].device, int(np.prod(self.tt_q_shapes)), stop - start
+        if out is None:
+            out = torch.empty((n, D), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or tuple(out.shape) != (n, D):
+            raise ValueError(f"dense_rows: out must be a contiguous float32 tensor of shape {(n, D)} on {dev}, got "
+                             f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        if n == 0:
+            return out
+        if not cores[0].is_cuda:
+            out.copy_(_svd.tt_full(self.table_cores(k), E)[start:stop])
+            return out
+        geom = (self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks)
+        if _engine.tt_expand_supported(*geom):
+            return _engine.tt_expand(self.num_tables, D, *geom[1:], k, start, stop, cores, out)
+        # two or four cores, large ranks: the rows kernels over consecutive indices, table k's own slices as a one-table geometry
+        for b in range(start, stop, self._DENSE_ROWS_BLOCK):
+            e = min(stop, b + self._DENSE_ROWS_BLOCK)
+            out[b - start:e - start] = _engine.tt_rows(1, D, p, self.tt_q_shapes, self.tt_ranks,
+                                                       torch.arange(b, e, dtype=torch.int64, device=dev), None, one)
+        return out
 
     # ------------------------------------------------- canonical cores, from_pretrained, truncate_ranks (DESIGN.md 4.18)
     def _table_index(self, table: int) -> int:

@@ -293,6 +293,10 @@ class VarTableTTEmbeddingBag(TableBatchedTTEmbeddingBag):
         k = self._table_index(table)
         return _ops._svd.tt_full(self.table_cores(k), self.table_num_embeddings[k])
 
+    def _table_view(self, k: int):
+        self._no_table_q("dense_rows")
+        return self.table_num_embeddings[k], list(self.tt_p_shapes[k]), [self.table_rows(t)[k].unsqueeze(0) for t in range(self.tt_ndim)]
+
     # ------------------------------------------------- canonical cores, from_pretrained
     def _no_table_q(self, what: str) -> None:
         if self.table_q is not None:
@@ -634,6 +638,26 @@ class MixedTTEmbeddingBag(nn.Module):
         if dense:
             return mod.table_weight(j).clone()
         return mod.full_weight(j)[:self.num_embeddings[int(table) % len(self.num_embeddings)]]
+
+    def dense_rows(self, table: int, start: int = 0, stop: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """rows [start, stop) of table k as a dense [stop - start, D] tensor (`stop` None: the table's num_embeddings): a TT member's
+        from its cores (the group's dense_rows: one HIP kernel), a dense member's a copy of that slice of its weight"""
+        mod, j, dense = self._member(table)
+        E = self.num_embeddings[int(table) % len(self.num_embeddings)]
+        start, stop = int(start), E if stop is None else int(stop)
+        if not 0 <= start <= stop:
+            raise IndexError(f"dense_rows: [{start}, {stop}) is not a range of rows")
+        if stop > E:
+            raise IndexError(f"dense_rows: stop={stop} is beyond the table's {E} rows")
+        if not dense:
+            return mod.dense_rows(start, stop, j, out)
+        w = mod.table_weight(j)
+        rows = w.detach()[start:stop]
+        if out is None:
+            return rows.clone()
+        if out.dtype != rows.dtype or not out.is_contiguous() or out.device != rows.device or out.shape != rows.shape:
+            raise ValueError(f"dense_rows: out must be a contiguous {rows.dtype} tensor of shape {tuple(rows.shape)} on {rows.device}")
+        return out.copy_(rows)
 
     @classmethod
     def from_pretrained(cls, embeddings, tt_ranks=None, tt_p_shapes: Optional[Sequence[Optional[List[int]]]] = None,

@@ -988,6 +988,34 @@ int ttx_tt_rows_bf16m(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* 
                       const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
                       ttx_stream_t stream);
 
+/* ---- dense rows: a range of a table expanded (csrc/ttx_tt_expand.hip; not in the reference) -------------------
+ * out[n - row_begin, :] = the TT row of index n of table `table`, for row_begin <= n < row_end, from the fp32 cores in their
+ * ordinary layout (cores: a HOST array of 3 device pointers, as tt_cores everywhere).  The one operation that takes no indices:
+ * no plan, no sort, no workspace; the grid is arithmetic on row_begin, row_end and the table's p.  A surface of its own: every
+ * entry point above returns exactly what it returned before it existed.
+ * SUPPORTED (ttx_tt_expand_supported: host-side, stateless, touches no device; any p, any num_tables, p_tables or not):
+ *   T == 3, r1 <= 128 and r2 <= 128, q0 <= 16, q1 <= 64, q2 <= 32, and the fp32 x_0 of ONE (i0, i1) prefix, q0 q1 rows of
+ *   XS = K2p (+ 4 where K2p / 4 is even) floats with K2p = r2 rounded up to 4, within 64 KiB of LDS.  Everything else returns 0
+ *   here and TTX_EUNSUPPORTED from ttx_tt_expand.
+ * ROWS  out [row_end - row_begin, D] float32, D = prod(q).  Row n = (i0 p1 + i1) p2 + i2: one work-group of 256 threads takes a
+ *   prefix (i0, i1) that meets the range (the first and the last may be partial), computes x_0 = core_0[i0] core_1[i1] ONCE on
+ *   mfma_f32_16x16x4f32 into LDS, and multiplies it with the prefix's contiguous core-2 slices on the same instruction; a lane
+ *   stores four consecutive c of one row (16 bytes where q2 % 4 == 0 and out is 16-byte aligned, scalar stores otherwise).  A
+ *   range of fewer than 1024 prefixes spreads the i2 of a prefix over several work-groups, each of which recomputes x_0.
+ *   p_tables: table k's own p and slice bases.  prod(p) may exceed 2^31 (64-bit row arithmetic); a core of at most 2^30 slices.
+ *   One writer per element, no atomics: bit-identical from run to run; nothing read back, nothing allocated: capturable.
+ *   row_begin == row_end returns 0 and launches nothing; nothing outside out[0 .. (row_end - row_begin) D) is written.
+ * NUMERICS  against the float64 chain product of the same fp32 cores (the fp32 term of the bf16 forward's bound):
+ *     |err(row[a, b, c])| <= (r1 + r2 + 2) 2^-24 sum_{k1, k2} |c_0[a, k1]| |c_1[k1, (b, k2)]| |c_2[k2, c]|
+ * ERRORS  -1 (TTX_EINVAL) with ttx_last_error() set, before anything touches a device: a NULL geometry, T outside 2..4,
+ *   num_tables <= 0, table outside [0, num_tables), a p <= 0 or > 2^30, prod(p) > 2^62, row_begin < 0, row_end < row_begin,
+ *   row_end > prod(p of that table); with a range that is not empty, NULL cores / out or a pointer not 4-byte aligned.
+ *   TTX_EUNSUPPORTED for a shape
+ *   ttx_tt_expand_supported rejects (checked before the table and the range). */
+int ttx_tt_expand_supported(const ttx_geom* g);
+int ttx_tt_expand(const ttx_geom* g, int32_t table, int64_t row_begin, int64_t row_end, const float* const* cores, float* out,
+                  ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
