@@ -4,6 +4,7 @@
     python examples/serve_bf16.py            # on cuda:0
     python examples/serve_bf16.py --wide     # TT ranks 96: the column-blocked bf16 kernel (route "bf16w")
     python examples/serve_bf16.py --mfma-tail  # D = 1024, q = [8, 8, 16]: both products on the bf16 MFMA (route "bf16m")
+    python examples/serve_bf16.py --hot 4096   # keep the 4096 most visited rows of a skewed stream expanded
 
 1. a dense table (low TT rank plus noise) stands in for a trained nn.EmbeddingBag;
 2. `TTEmbeddingBag.from_pretrained` factors it by TT-SVD into an ordinary module;
@@ -12,11 +13,14 @@
    serves the same rounded weights through the fp32 kernels; `from_module(trained, wide=True)` opts in to the column-blocked
    bf16 kernel for ranks up to 128 and wide q1: `served.route == "bf16w"`; `from_module(trained, mfma_tail=True)` to the
    kernel for a last factor q2 up to 32, the default factorings of widths from 640 up: `served.route == "bf16m"`);
-4. a batch is served and compared with the fp32 module and with the dense table."""
+4. a batch is served and compared with the fp32 module and with the dense table;
+5. with `--hot N` the stream is skewed (Zipf 1.2) and `from_module(trained, hot_indices=...)` keeps its N most visited rows as bf16
+   rows beside the cores: their lookups are pooled from that table, only the misses are contracted."""
 import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -28,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wide", action="store_true", help="factor at TT ranks 96 and serve on the column-blocked bf16 kernel")
     ap.add_argument("--mfma-tail", action="store_true", help="a table of width 1024 (q = [8, 8, 16]) served on the MFMA-tail bf16 kernel")
+    ap.add_argument("--hot", type=int, default=0, metavar="N", help="serve the N most visited rows of a Zipf 1.2 stream from a hot row table")
     args = ap.parse_args()
     wide, tail = args.wide, args.mfma_tail
     import tt_embeddings_ops as ops
@@ -44,14 +49,22 @@ def main():
     bag = nn.EmbeddingBag.from_pretrained(weight, freeze=True, mode="sum", include_last_offset=True)
 
     trained = ops.TTEmbeddingBag.from_pretrained(weight, [96, 96] if wide else [16, 16], p, q, device=dev, use_cache=False)
-    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide, mfma_tail=tail)
+    B, L = 512, 8
+    idx = torch.randint(0, E, (B * L,), device=dev)
+    hot = None
+    if args.hot > 0:  # a skewed stream, and its most visited rows (in production: counted over yesterday's traffic)
+        ranks = torch.from_numpy((np.random.RandomState(0).zipf(1.2, size=B * L) - 1) % E).to(dev)
+        idx = torch.randperm(E, device=dev)[ranks]
+        rows, counts = torch.unique(idx, return_counts=True)
+        hot = rows[torch.argsort(counts, descending=True)[:args.hot]]
+    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide, mfma_tail=tail, hot_indices=hot)
     print(served)
+    if hot is not None:
+        print(f"hot rows {served.hot_rows_count}: {torch.isin(idx, hot).float().mean().item():.1%} of the batch's lookups are served from them")
     print(f"route {served.route}; parameters {len(list(served.parameters()))}; "
           f"buffers {sum(b.numel() * b.element_size() for b in served.buffers()) / 1e3:.0f} kB "
           f"(fp32 cores: {sum(c.numel() * 4 for c in trained.tt_cores) / 1e3:.0f} kB, dense table: {weight.numel() * 4 / 1e6:.1f} MB)")
 
-    B, L = 512, 8
-    idx = torch.randint(0, E, (B * L,), device=dev)
     off = torch.arange(0, B * L + 1, L, device=dev)
     out = served(idx, off)
     with torch.no_grad():

@@ -238,6 +238,10 @@ def _load(path):
     L.ttx_tt_expand_supported.argtypes = [G]
     L.ttx_tt_expand.argtypes = [G, i32, i64, i64, vp, vp, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
+    # hot rows of the inference forward (and the prologue of a device-side count, which the split's misses take)
+    L.ttx_lookup_prologue_n.argtypes = [G, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, sz, vp, vp]
+    L.ttx_hot_probe_pool.argtypes = [i32, i64, i32, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]
+    L.ttx_bag_sum_pool_add.argtypes = [i64, i32, vp, vp, vp, vp, vp]
     return L
 
 
@@ -470,12 +474,33 @@ def split0_expand(indices: torch.Tensor, offsets: torch.Tensor, k: int, p_rest: 
 
 
 def lookup_prologue(colidx: torch.Tensor, offsets: torch.Tensor, num_tables: int, tt_p_shapes, tt_q_shapes, tt_ranks,
-                    hashtbl: Optional[torch.Tensor] = None, cache_freq: Optional[torch.Tensor] = None
-                    ) -> Tuple[torch.Tensor, torch.Tensor, Optional[Plan]]:
+                    hashtbl: Optional[torch.Tensor] = None, cache_freq: Optional[torch.Tensor] = None,
+                    n_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, Optional[Plan]]:
     """Not in the reference: update_cache_state (when hashtbl / cache_freq are given) +
     preprocess_indices_sync(warmup=True) + make_plan of one batch in ONE native call (one launch
-    when the batch qualifies, include/ttx.h).  -> (rowidx, tableidx, plan)."""
+    when the batch qualifies, include/ttx.h).  -> (rowidx, tableidx, plan).
+    `n_dev` (trailing keyword): one int32 on the device, the number of LEADING entries of colidx that are the batch
+    (offsets[-1] == n_dev <= colidx.numel(): bags_compact's outputs) -- only they are planned (ttx_lookup_prologue_n)."""
     dev = _dev(colidx)
+    if n_dev is not None:
+        if hashtbl is not None or cache_freq is not None:
+            raise RuntimeError("tt_embeddings: lookup_prologue(n_dev=) does not take a frequency table")
+        if n_dev.dtype != torch.int32 or n_dev.numel() != 1 or n_dev.device != dev:
+            raise RuntimeError(f"tt_embeddings: n_dev must be one int32 on {dev}, got {n_dev.dtype} x {n_dev.numel()} on {n_dev.device}")
+        colidx, offsets = _i64(colidx, "colidx"), _i64(offsets, "offsets")
+        nnz = colidx.numel()
+        rowidx, tableidx = torch.empty_like(colidx), torch.empty_like(colidx)
+        if nnz == 0:
+            return rowidx, tableidx, None
+        g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+        L = lib()
+        nb = L.ttx_plan_bytes(C.byref(g), nnz)
+        buf = torch.empty(nb, dtype=torch.uint8, device=dev)
+        with _guard(dev):
+            _check(L.ttx_lookup_prologue_n(C.byref(g), nnz, colidx.data_ptr(), offsets.numel() - 1, offsets.data_ptr(), 0, None,
+                                           None, rowidx.data_ptr(), tableidx.data_ptr(), buf.data_ptr(), nb, n_dev.data_ptr(),
+                                           _stream(dev)))
+        return rowidx, tableidx, Plan(buf, nnz, (num_tables, tuple(tt_p_shapes), tuple(tt_q_shapes), tuple(tt_ranks)))
     colidx, offsets = _i64(colidx, "colidx"), _i64(offsets, "offsets")
     nnz = colidx.numel()
     rowidx = torch.empty_like(colidx)
@@ -1279,6 +1304,43 @@ def bag_sum_pool(rows: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
     with _guard(dev):
         _check(lib().ttx_bag_sum_pool(nb, D, offsets.data_ptr(), rows.data_ptr(), out.data_ptr(), _stream(dev)))
     return out
+
+
+# ---- hot rows of the inference forward (include/ttx.h "hot rows of the inference forward"; ttx_infer.TTInferenceBag) ----
+def hot_probe_pool(indices: torch.Tensor, offsets: torch.Tensor, num_tables: int, key_stride: int, hot_keys: torch.Tensor,
+                   hot_rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (masked_indices [nnz] int64: -1 at a slot whose key table * key_stride + index is in hot_keys, the index elsewhere;
+    hit_sum [nb, D] float32: the sum of each bag's hit rows).  offsets with their closing entry, num_tables * B bags, table-major;
+    hot_keys [K] int64 ascending, hot_rows [K, D] bfloat16.  One launch."""
+    dev = _dev(indices)
+    indices, offsets, hot_keys = _i64(indices, "indices"), _i64(offsets, "offsets"), _i64(hot_keys, "hot_keys")
+    nb, K = offsets.numel() - 1, hot_keys.numel()
+    if hot_rows.dtype != torch.bfloat16 or not hot_rows.is_contiguous() or hot_rows.dim() != 2 or hot_rows.size(0) != K \
+            or hot_rows.device != dev or hot_keys.device != dev:
+        raise RuntimeError(f"tt_embeddings: hot_rows must be a contiguous bfloat16 [{K}, D] beside hot_keys on {dev}")
+    if nb < 0 or nb % num_tables != 0:
+        raise RuntimeError(f"tt_embeddings: offsets must describe num_tables * B bags, got {nb} bags for {num_tables} tables")
+    D = hot_rows.size(1)
+    masked = torch.empty_like(indices)
+    hit = torch.empty((nb, D), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(lib().ttx_hot_probe_pool(num_tables, nb // num_tables, D, indices.numel(), indices.data_ptr(), offsets.data_ptr(),
+                                        int(key_stride), K, hot_keys.data_ptr(), hot_rows.data_ptr(), masked.data_ptr(),
+                                        hit.data_ptr(), _stream(dev)))
+    return masked, hit
+
+
+def bag_sum_pool_add(rows: torch.Tensor, offsets: torch.Tensor, addend: torch.Tensor) -> torch.Tensor:
+    """addend[b, :] += the fp32 sum of bag b's rows in index order (bag_sum_pool started from the addend), in place -> addend"""
+    dev = _dev(rows)
+    rows, offsets = _f32(rows, "rows"), _i64(offsets, "offsets")
+    nb, D = offsets.numel() - 1, rows.size(1)
+    if addend.dtype != torch.float32 or not addend.is_contiguous() or addend.device != dev or tuple(addend.shape) != (nb, D):
+        raise RuntimeError(f"tt_embeddings: addend must be a contiguous float32 {(nb, D)} on {dev}")
+    with _guard(dev):
+        _check(lib().ttx_bag_sum_pool_add(nb, D, offsets.data_ptr(), rows.data_ptr(), addend.data_ptr(), addend.data_ptr(),
+                                          _stream(dev)))
+    return addend
 
 
 def bag_max_pool(rows: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -20,8 +20,18 @@ geometries the two above refuse for their last factor -- q2 up to 32, the defaul
 `route == "bf16m"`, core 2 packed transposed, `tt_rows_bf16m`.  It rounds x_0 once to bf16: within the same bound, not bit-equal
 to the fp32 route.  Routes are tried in the order "bf16", "bf16w" (with `wide`), "bf16m" (with `mfma_tail`), "fp32".
 
-Limits: no fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, no live row
-cache, not the mixed-cardinality or sharded module classes (the C entry points do take p_tables geometries); nothing trains."""
+`from_module(trained, hot_indices=rows)` (one 1-D int64 tensor, or one per table) keeps those rows EXPANDED beside the cores
+(DESIGN.md 4.23): computed once through the module's own route, rounded to bf16, as the buffers `hot_keys` [K] (sorted, key =
+table * num_embeddings + index) and `hot_rows` [K, D]; `hot_rows_count` is K.  A call then probes the table, pools the hits from
+it, compacts the misses on the device and contracts only those (`hot_probe_pool`, `bags_compact`, the prologue and rows kernel on
+the live count, `bag_sum_pool_add`): a bag is its hits in slot order, then its misses in slot order -- within the bound, not
+bit-equal to the module without the table.  `from_module(cached, hot_from_cache=True)` freezes a module whose row cache is LIVE:
+the hot set is what it holds cached, the hot rows are its trained `cache_weight` rows.  Routes "bf16", "bf16w" and "bf16m"; the
+"fp32" route refuses a hot table (its twin hands out no rows).  Without either argument nothing changes.
+
+Limits: no fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, a live row
+cache only as the hot table above (which is fixed at freeze time), not the mixed-cardinality or sharded module classes (the C
+entry points do take p_tables geometries); nothing trains."""
 from typing import List, Optional, Sequence
 
 import torch
@@ -87,7 +97,8 @@ class TTInferenceBag(nn.Module):
         self.route = "bf16"
 
     @classmethod
-    def from_module(cls, module: nn.Module, wide: bool = False, mfma_tail: bool = False) -> "TTInferenceBag":
+    def from_module(cls, module: nn.Module, wide: bool = False, mfma_tail: bool = False, hot_indices=None,
+                    hot_from_cache: bool = False) -> "TTInferenceBag":
         if not isinstance(module, _ops.TableBatchedTTEmbeddingBag) or isinstance(module.tt_p_shapes[0], (list, tuple)) \
                 or hasattr(module, "_p_flat"):
             raise TypeError("TTInferenceBag.from_module takes a TTEmbeddingBag, a TableBatchedTTEmbeddingBag or a TTEmbedding, got "
@@ -97,10 +108,15 @@ class TTInferenceBag(nn.Module):
             raise ValueError("TTInferenceBag: mode='max' is not supported (the inference path pools by sum or mean)")
         if module.__dict__.get("padding_idx") is not None:
             raise ValueError("TTInferenceBag: a module with padding_idx is not supported")
-        if module.use_cache and not module.warmup:
+        live = bool(module.use_cache and not module.warmup)
+        if live and not hot_from_cache:
             raise ValueError("TTInferenceBag: the module's row cache is live -- its cached rows were trained away from the cores, "
                              "and a copy of the cores would serve stale rows; fold them back with cache_populate(write_back=...) "
                              "and reset_cache(), or freeze a fresh module")
+        if hot_from_cache and not live:
+            raise ValueError("TTInferenceBag: hot_from_cache=True takes a module whose row cache is live (after cache_populate())")
+        if hot_from_cache and hot_indices is not None:
+            raise ValueError("TTInferenceBag: give hot_indices or hot_from_cache=True, not both")
         self = cls()
         self.kind = "embedding" if isinstance(module, _ops.TTEmbedding) else \
             ("bag" if isinstance(module, _ops.TTEmbeddingBag) else "batched")
@@ -118,6 +134,10 @@ class TTInferenceBag(nn.Module):
             self.route = "bf16m"  # (opt-in: both products on the MFMA, q2 up to 32)
         else:
             self.route = "fp32"
+        if self.route == "fp32" and (hot_from_cache or hot_indices is not None):
+            raise ValueError("TTInferenceBag: a hot row table is not served on route 'fp32' -- the twin pools inside its own forward "
+                             "and hands out no rows for a compacted batch to add to the hits' sums; it needs a geometry of the "
+                             "bf16 kernels (three cores; wide=True / mfma_tail=True widen the domain)")
         if self.route != "fp32":
             if cores[0].is_cuda:
                 pack = {"bf16": _engine.pack_cores_bf16, "bf16w": _engine.pack_cores_bf16w, "bf16m": _engine.pack_cores_bf16m}
@@ -137,11 +157,87 @@ class TTInferenceBag(nn.Module):
             del twin.tt_cores
             twin.tt_cores = _ops.BufferList("tt_cores", [c.to(torch.bfloat16).float() for c in cores])
             self.fp32 = twin
+        if hot_from_cache:
+            self._hot_from_cache(module)
+        elif hot_indices is not None:
+            self._hot_from_indices(hot_indices, cores[0].device)
         return self
 
+    # ------------------------------------------------------------------ the hot row table
+    @property
+    def hot_rows_count(self) -> int:
+        """K: rows served from the hot table (0: there is none, and a call is what it was without one)"""
+        return int(self.hot_keys.numel()) if hasattr(self, "hot_keys") else 0
+
+    def _set_hot(self, keys: torch.Tensor, rows: torch.Tensor) -> None:
+        """keys ascending and distinct, rows [K, D] bf16 in their order; K == 0 registers nothing"""
+        if keys.numel() > 0:
+            self.register_buffer("hot_keys", keys.contiguous())
+            self.register_buffer("hot_rows", rows.contiguous())
+
+    def _hot_from_indices(self, hot_indices, dev: torch.device) -> None:
+        per_table = [hot_indices] if isinstance(hot_indices, torch.Tensor) else list(hot_indices)
+        if len(per_table) != self.num_tables:
+            raise ValueError(f"hot_indices: one 1-D int64 tensor per table, got {len(per_table)} for {self.num_tables} tables")
+        E, keys = self.num_embeddings, []
+        for t, idx in enumerate(per_table):
+            if not isinstance(idx, torch.Tensor) or idx.dim() != 1 or idx.dtype != torch.int64:
+                raise ValueError(f"hot_indices[{t}] must be a 1-D int64 tensor")
+            if idx.numel() > 0 and (int(idx.min()) < 0 or int(idx.max()) >= E):
+                raise ValueError(f"hot_indices[{t}] holds a row outside [0, {E})")
+            keys.append(torch.unique(idx.to(dev)) + t * E)  # (sorted; table-major: ascending as a whole)
+        keys = torch.cat(keys)
+        if keys.numel() == 0:
+            return
+        idx, tab = keys % E, keys // E
+        rows = self._rows_hip(idx, tab) if keys.is_cuda else self._rows_torch(idx, tab)  # the frozen module's own route
+        self._set_hot(keys, rows.to(torch.bfloat16))
+
+    def _hot_from_cache(self, module: nn.Module) -> None:
+        """the keys the source holds cached and their cache_weight rows, read from its cache state on the host.  The source keys by
+        table * prod(tt_p_shapes) + index; a cached index beyond num_embeddings has no key here and is left to the cores."""
+        state, tbl = module.cache_state.cpu(), module.hashtbl.cpu()
+        slots = torch.nonzero(state >= 0).flatten()
+        src, loc = tbl[slots], state[slots].long()
+        stride, E = module._key_stride(), self.num_embeddings
+        tab, idx = src // stride, src % stride
+        keep = (src >= 0) & (idx < E) & (tab < self.num_tables)
+        keys, order = torch.sort(tab[keep] * E + idx[keep], stable=True)
+        loc = loc[keep][order]
+        first = torch.ones_like(keys, dtype=torch.bool)
+        first[1:] = keys[1:] != keys[:-1]  # (a key seated twice: the lower slot's row)
+        dev = module.cache_weight.device
+        rows = module.cache_weight.detach()[loc[first].to(dev)].to(torch.bfloat16)
+        self._set_hot(keys[first].to(dev), rows)
+
+    def _forward_hot(self, flat: torch.Tensor, offsets: torch.Tensor, tables: int) -> torch.Tensor:
+        """-> [bags, D]: every bag's hit rows from the table, then its miss rows from the cores (sum; the mean on top)"""
+        E, D, nb = self.num_embeddings, self.embedding_dim, offsets.numel() - 1
+        if flat.is_cuda:
+            masked, out = _engine.hot_probe_pool(flat, offsets, tables, E, self.hot_keys, self.hot_rows)
+            misses, miss_off, n_live = _engine.bags_compact(masked, offsets, 0, -1)
+            _, tableidx, plan = _engine.lookup_prologue(misses, miss_off, tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks,
+                                                        n_dev=n_live)
+            rows = self._rows_hip(misses, tableidx, plan)
+            out = _engine.bag_sum_pool_add(rows, miss_off, out)
+            return _engine.bag_mean_scale(out, offsets) if self.mode == "mean" else out
+        lens = offsets[1:] - offsets[:-1]
+        bag = torch.repeat_interleave(torch.arange(nb, dtype=torch.int64), lens)
+        tab = bag // (nb // tables)
+        inside = (flat >= 0) & (flat < E)
+        key = torch.where(inside, tab * E + flat, torch.zeros_like(flat))
+        pos = torch.searchsorted(self.hot_keys, key).clamp(max=self.hot_rows_count - 1)
+        hit = inside & (self.hot_keys[pos] == key)
+        out = torch.zeros((nb, D), dtype=torch.float32).index_add_(0, bag[hit], self.hot_rows[pos[hit]].float())
+        out.index_add_(0, bag[~hit], self._rows_torch(flat[~hit], tab[~hit]))
+        if self.mode == "mean":
+            out = out / lens.clamp(min=1).to(torch.float32).unsqueeze(1)
+        return out
+
     def extra_repr(self) -> str:
+        hot = f", hot_rows={self.hot_rows_count}" if self.hot_rows_count else ""
         return (f"{self.kind}, route={self.route}, num_tables={self.num_tables}, p={self.tt_p_shapes}, q={self.tt_q_shapes}, "
-                f"ranks={self.tt_ranks[1:-1]}, mode={self.mode}")
+                f"ranks={self.tt_ranks[1:-1]}, mode={self.mode}{hot}")
 
     def _packed(self) -> List[torch.Tensor]:
         return [self.packed_core0, self.packed_core1, self.packed_core2]
@@ -197,6 +293,9 @@ class TTInferenceBag(nn.Module):
             flat = indices.reshape(-1).long().contiguous()
             if flat.numel() == 0:
                 return torch.zeros(tuple(indices.shape) + (D,), dtype=torch.float32, device=indices.device)
+            if self.hot_rows_count:  # (the positions as bags of one slot)
+                one = torch.arange(flat.numel() + 1, dtype=torch.int64, device=flat.device)
+                return self._forward_hot(flat, one, 1).view(tuple(indices.shape) + (D,))
             if flat.is_cuda:
                 rows = self._rows_hip(flat, None)
             else:
@@ -210,6 +309,8 @@ class TTInferenceBag(nn.Module):
         shape = (B, D) if self.kind == "bag" else (self.num_tables, B, D)
         if flat.numel() == 0:
             return torch.zeros(shape, dtype=torch.float32, device=flat.device)
+        if self.hot_rows_count:
+            return self._forward_hot(flat, offsets, self.num_tables).view(shape)
         if flat.is_cuda:
             _, tableidx, plan = _engine.lookup_prologue(flat, offsets, self.num_tables, self.tt_p_shapes, self.tt_q_shapes,
                                                         self.tt_ranks)

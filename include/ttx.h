@@ -1016,6 +1016,39 @@ int ttx_tt_expand_supported(const ttx_geom* g);
 int ttx_tt_expand(const ttx_geom* g, int32_t table, int64_t row_begin, int64_t row_end, const float* const* cores, float* out,
                   ttx_stream_t stream);
 
+/* ---- hot rows of the inference forward (csrc/ttx_hot.hip; not in the reference) ------------------------------
+ * A frozen table's most visited rows kept expanded beside its packed cores: hot_keys [K] int64, strictly ascending, key =
+ * table * key_stride + index; hot_rows [K, D] bf16, row i the row of hot_keys[i].  A surface of its own: every entry point above
+ * returns exactly what it returned before it existed.  A served call is ttx_hot_probe_pool, ttx_bags_compact(padding_idx = -1),
+ * ttx_lookup_prologue_n + a rows kernel on the live count, ttx_bag_sum_pool_add, and ttx_bag_mean_scale with the ORIGINAL offsets
+ * for the mean.
+ * PROBE + POOL  ttx_hot_probe_pool, ONE launch over the table-major batch of num_tables * B bags (offsets [num_tables B + 1],
+ *   closing entry included, entries clamped to [0, nnz]):
+ *     masked_indices[n]  -1 where slot n is a hit (its key is in hot_keys); else the index, a negative index as 0 (a miss, as
+ *                        the rows kernels clamp it); an index >= key_stride is a miss and is passed on as it is; -1 at the slots in
+ *                        front of offsets[0] and from offsets[nb] on.  All nnz elements are written.
+ *     hit_sum[b, :]      float32 [num_tables B, D]: the sum of bag b's hit rows, each widened exactly, +0 where the bag has none.
+ *                        Every element is written; no memset runs in front.
+ *   One wave per bag: up to 64 slots probed at once (branch-free lower bound, every address inside hot_keys), the hits' rows
+ *   accumulated in fp32 per lane group in slot order (64 / LPR groups; 16-byte loads of 8 bf16 where D % 8 == 0 and hot_rows and
+ *   hit_sum are 16-byte aligned, scalar otherwise), the groups combined pairwise.  K == 0: every slot is a miss.
+ * POOL  ttx_bag_sum_pool_add: output[b, :] = addend[b, :] + rows[offsets[b], :] + rows[offsets[b] + 1, :] + ... in index order:
+ *   ttx_bag_sum_pool started from the addend, the same access widths (16-byte when D % 4 == 0 and the three float pointers are
+ *   16-byte aligned).  output may alias addend.
+ * SUMMATION ORDER of a served bag: its hits in slot order (by lane group), then its misses in slot order.  Results with a hot
+ *   table are within the bound of the bf16 forward -- a hit row adds no error of its own, only its share of len 2^-24 sum |row| --
+ *   but not bit-equal to the result without one.
+ * No atomics, one writer per element: bit-identical from run to run; nothing read back, nothing allocated: capturable.
+ * nnz == 0 or nb == 0 returns 0 and launches nothing.
+ * ERRORS  -1 (TTX_EINVAL) with ttx_last_error() set, before anything touches a device: num_tables <= 0, a negative B / nnz / K,
+ *   D <= 0, key_stride <= 0 or num_tables * key_stride > 2^62, nnz, K or nb >= 2^31, a NULL pointer that would be read or written
+ *   (hot_keys / hot_rows only with K > 0), an int64 array not 8-byte, a float array not 4-byte aligned. */
+int ttx_hot_probe_pool(int32_t num_tables, int64_t B, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* offsets,
+                       int64_t key_stride, int64_t K, const int64_t* hot_keys, const void* hot_rows_bf16, int64_t* masked_indices,
+                       float* hit_sum, ttx_stream_t stream);
+int ttx_bag_sum_pool_add(int64_t nb, int32_t D, const int64_t* offsets, const float* rows, const float* addend, float* output,
+                         ttx_stream_t stream);
+
 /* test entry: the stable descending 64-bit radix sort of (key, value) pairs behind ttx_cache_populate, on its own
  * (what the reference asks of cub::DeviceRadixSort::SortPairsDescending, tt_embeddings_cuda.cu:1280-1308).  Stateless. */
 size_t ttx_debug_sort_workspace_bytes(int64_t n);
