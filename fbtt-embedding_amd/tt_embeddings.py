@@ -235,6 +235,13 @@ def _load(path):
     L.ttx_tt_rows_bf16m_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_rows_bf16m_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_rows_bf16m.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_tt_rows_bf16q_supported.argtypes = [G]
+    L.ttx_tt_pack_bf16q_elems.restype = i64
+    L.ttx_tt_pack_bf16q_elems.argtypes = [G, i32]
+    L.ttx_tt_pack_bf16q.argtypes = [G, i32, vp, vp, vp]
+    L.ttx_tt_rows_bf16q_workspace_bytes.restype = C.c_size_t
+    L.ttx_tt_rows_bf16q_workspace_bytes.argtypes = [G, i32, i64]
+    L.ttx_tt_rows_bf16q.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
     L.ttx_tt_expand_supported.argtypes = [G]
     L.ttx_tt_expand.argtypes = [G, i32, i64, i64, vp, vp, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
@@ -1186,7 +1193,8 @@ def tt_rows_bf16m_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> b
 
 
 def _pack_cores_bf(kind, num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
-    """kind: "bf16" (the narrow kernel's entry points), "bf16w" (the column-blocked kernel's) or "bf16m" (the MFMA-tail kernel's)"""
+    """kind: "bf16" (the narrow kernel's entry points), "bf16w" (the column-blocked kernel's), "bf16m" (the MFMA-tail kernel's) or
+    "bf16q" (the four-core kernel's)"""
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
     dev = _dev(tt_cores[0])
     cores = _cores(tt_cores, g)
@@ -1208,8 +1216,9 @@ def _pack_cores_bf(kind, num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_core
 def _tt_rows_bf(kind, num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan) -> torch.Tensor:
     g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
     dev = _dev(packed_cores[0])
-    if len(packed_cores) != 3 or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
-        raise RuntimeError(f"tt_embeddings: tt_rows_{kind} needs the three packed bfloat16 cores of pack_cores_{kind} on one device")
+    ncores = 4 if kind == "bf16q" else 3
+    if len(packed_cores) != ncores or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
+        raise RuntimeError(f"tt_embeddings: tt_rows_{kind} needs the {ncores} packed bfloat16 cores of pack_cores_{kind} on one device")
     lb = lib()
     elems = getattr(lb, f"ttx_tt_pack_{kind}_elems")
     for t, c in enumerate(packed_cores):
@@ -1263,6 +1272,26 @@ def tt_rows_bf16m(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, ta
                   plan: Optional[Plan] = None) -> torch.Tensor:
     """tt_rows_bf16 on the MFMA-tail kernel (q2 up to 32, both products on the bf16 MFMA) from the cores of pack_cores_bf16m"""
     return _tt_rows_bf("bf16m", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
+
+
+def tt_rows_bf16q_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the four-core bf16 rows kernel take this geometry (T = 4, ranks <= 64, q0 <= 16, q1 <= 64, q3 <= 16, q2 q3 <= 32, the
+    x_0 and M of one lookup within a work-group's LDS)?  Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_rows_bf16q_supported(C.byref(g)))
+
+
+def pack_cores_bf16q(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores) -> List[torch.Tensor]:
+    """pack_cores_bf16 for the four-core kernel (tt_rows_bf16q_supported): cores 0 and 1 in the same layout, core 2 in its natural
+    order with k3 padded ([r2 q2][K3p]), core 3 transposed ([16][K3p], its k3 index contiguous)"""
+    return _pack_cores_bf("bf16q", num_tables, tt_p_shapes, tt_q_shapes, tt_ranks, tt_cores)
+
+
+def tt_rows_bf16q(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores,
+                  plan: Optional[Plan] = None) -> torch.Tensor:
+    """tt_rows_bf16 for a four-core table (all three products on the bf16 MFMA, x_0 and the merged last cores in LDS) from the
+    four cores of pack_cores_bf16q"""
+    return _tt_rows_bf("bf16q", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
 
 
 # ---- dense rows: a range of a table expanded (include/ttx.h "dense rows"; the method on top: dense_rows of the modules) ----

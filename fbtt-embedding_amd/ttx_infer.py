@@ -18,7 +18,13 @@ one refuses -- ranks up to 128, any q1 <= 64: `route == "bf16w"`, the same packe
 `from_module(trained, mfma_tail=True)` opts in to the kernel that runs BOTH products on the bf16 MFMA for the
 geometries the two above refuse for their last factor -- q2 up to 32, the default factorings of every width from 640 up:
 `route == "bf16m"`, core 2 packed transposed, `tt_rows_bf16m`.  It rounds x_0 once to bf16: within the same bound, not bit-equal
-to the fp32 route.  Routes are tried in the order "bf16", "bf16w" (with `wide`), "bf16m" (with `mfma_tail`), "fp32".
+to the fp32 route.
+
+`from_module(trained, four_cores=True)` opts in to the four-core kernel for tables of FOUR cores with ranks
+<= 64 and q2 q3 <= 32: `route == "bf16q"`, four packed buffers, `tt_rows_bf16q` -- all three products on the bf16 MFMA in chain
+order (core_0 core_1) (core_2 core_3), both factors rounded once to bf16 in LDS: within its own bound (include/ttx.h), not
+bit-equal to the fp32 route.  Routes are tried in the order "bf16", "bf16w" (with `wide`), "bf16m" (with `mfma_tail`), "bf16q"
+(with `four_cores`), "fp32".
 
 `from_module(trained, hot_indices=rows)` (one 1-D int64 tensor, or one per table) keeps those rows EXPANDED beside the cores
 (DESIGN.md 4.23): computed once through the module's own route, rounded to bf16, as the buffers `hot_keys` [K] (sorted, key =
@@ -26,10 +32,11 @@ table * num_embeddings + index) and `hot_rows` [K, D]; `hot_rows_count` is K.  A
 it, compacts the misses on the device and contracts only those (`hot_probe_pool`, `bags_compact`, the prologue and rows kernel on
 the live count, `bag_sum_pool_add`): a bag is its hits in slot order, then its misses in slot order -- within the bound, not
 bit-equal to the module without the table.  `from_module(cached, hot_from_cache=True)` freezes a module whose row cache is LIVE:
-the hot set is what it holds cached, the hot rows are its trained `cache_weight` rows.  Routes "bf16", "bf16w" and "bf16m"; the
-"fp32" route refuses a hot table (its twin hands out no rows).  Without either argument nothing changes.
+the hot set is what it holds cached, the hot rows are its trained `cache_weight` rows.  Routes "bf16", "bf16w", "bf16m" and
+"bf16q"; the "fp32" route refuses a hot table (its twin hands out no rows).  Without either argument nothing changes.
 
-Limits: no fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, a live row
+Limits: the bf16 kernels take three cores, or four with ranks <= 64 and q2 q3 <= 32 (two cores, four beyond that: "fp32"); no
+fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, a live row
 cache only as the hot table above (which is fixed at freeze time), not the mixed-cardinality or sharded module classes (the C
 entry points do take p_tables geometries); nothing trains."""
 from typing import List, Optional, Sequence
@@ -47,10 +54,15 @@ def _pad_up(n: int, m: int) -> int:
 
 def packed_shapes(q: Sequence[int], ranks: Sequence[int], mfma_tail: bool = False):
     """(per-slice shape of each packed core, the valid extents inside it) of a three-core geometry; ranks = [1, r1, r2, 1];
-    mfma_tail: core 2 in the transposed layout of the MFMA-tail kernel, [Q2P = q2 up to 16][K2p = r2 up to 32]"""
-    q0, q1, q2 = (int(x) for x in q)
+    mfma_tail: core 2 in the transposed layout of the MFMA-tail kernel, [Q2P = q2 up to 16][K2p = r2 up to 32].  Four factors
+    in q (ranks = [1, r1, r2, r3, 1]): the layout of the four-core kernel, core 2 [r2 q2][K3p], core 3 transposed [16][K3p]"""
     r1, r2 = int(ranks[1]), int(ranks[2])
-    K1p, N1 = _pad_up(r1, 32), q1 * r2
+    K1p, N1 = _pad_up(r1, 32), int(q[1]) * r2
+    if len(q) == 4:
+        r3, K3p = int(ranks[3]), _pad_up(int(ranks[3]), 32)
+        return ([(int(q[0]), K1p), (_pad_up(N1, 16), K1p), (r2 * int(q[2]), K3p), (16, K3p)],
+                [(int(q[0]), r1), (N1, r1), (r2 * int(q[2]), r3), (int(q[3]), r3)])
+    q0, q1, q2 = (int(x) for x in q)
     last = ((_pad_up(q2, 16), _pad_up(r2, 32)), (q2, r2)) if mfma_tail else ((r2, 4 if q2 <= 4 else 8), (r2, q2))
     return ([(q0, K1p), (_pad_up(N1, 16), K1p), last[0]], [(q0, r1), (N1, r1), last[1]])
 
@@ -58,17 +70,20 @@ def packed_shapes(q: Sequence[int], ranks: Sequence[int], mfma_tail: bool = Fals
 def pack_cores_torch(cores: Sequence[torch.Tensor], q: Sequence[int], ranks: Sequence[int],
                      mfma_tail: bool = False) -> List[torch.Tensor]:
     """the packed bf16 layout of include/ttx.h with torch ops (any device): what ttx_tt_pack_bf16 (mfma_tail:
-    ttx_tt_pack_bf16m) writes, bit for bit"""
+    ttx_tt_pack_bf16m; four cores: ttx_tt_pack_bf16q) writes, bit for bit"""
     full, valid = packed_shapes(q, ranks, mfma_tail)
     r1, r2 = int(ranks[1]), int(ranks[2])
+    four = len(q) == 4
     out = []
     for t, c in enumerate(cores):
         c = c.detach().reshape(-1, c.size(-1))  # [slices, r q r']
         S = c.size(0)
         if t == 1:  # [r1][q1 r2] -> column-major: K contiguous per output column
             c = c.view(S, r1, -1).transpose(1, 2)
-        if t == 2 and mfma_tail:  # [r2][q2] -> [q2][r2]: K contiguous per output column
+        if t == 2 and mfma_tail and not four:  # [r2][q2] -> [q2][r2]: K contiguous per output column
             c = c.view(S, r2, -1).transpose(1, 2)
+        if t == 3:  # [r3][q3] -> [q3][r3]: K contiguous per output column
+            c = c.view(S, int(ranks[3]), -1).transpose(1, 2)
         c = c.reshape(S, *valid[t]).to(torch.bfloat16)
         pk = torch.zeros((S,) + full[t], dtype=torch.bfloat16, device=c.device)
         pk[:, :valid[t][0], :valid[t][1]] = c
@@ -83,7 +98,7 @@ def unpack_cores_torch(packed: Sequence[torch.Tensor], q: Sequence[int], ranks: 
     out = []
     for t, pk in enumerate(packed):
         c = pk.view(-1, *full[t])[:, :valid[t][0], :valid[t][1]].float()
-        if t == 1 or (t == 2 and mfma_tail):
+        if t == 1 or t == 3 or (t == 2 and mfma_tail and len(q) == 3):
             c = c.transpose(1, 2)
         out.append(c.reshape(c.size(0), -1).contiguous())
     return out
@@ -98,7 +113,7 @@ class TTInferenceBag(nn.Module):
 
     @classmethod
     def from_module(cls, module: nn.Module, wide: bool = False, mfma_tail: bool = False, hot_indices=None,
-                    hot_from_cache: bool = False) -> "TTInferenceBag":
+                    hot_from_cache: bool = False, four_cores: bool = False) -> "TTInferenceBag":
         if not isinstance(module, _ops.TableBatchedTTEmbeddingBag) or isinstance(module.tt_p_shapes[0], (list, tuple)) \
                 or hasattr(module, "_p_flat"):
             raise TypeError("TTInferenceBag.from_module takes a TTEmbeddingBag, a TableBatchedTTEmbeddingBag or a TTEmbedding, got "
@@ -132,15 +147,18 @@ class TTInferenceBag(nn.Module):
             self.route = "bf16w"  # (opt-in: the column-blocked kernel where the narrow one refuses)
         elif mfma_tail and _engine.tt_rows_bf16m_supported(*geom):
             self.route = "bf16m"  # (opt-in: both products on the MFMA, q2 up to 32)
+        elif four_cores and _engine.tt_rows_bf16q_supported(*geom):
+            self.route = "bf16q"  # (opt-in: four cores, all three products on the MFMA)
         else:
             self.route = "fp32"
         if self.route == "fp32" and (hot_from_cache or hot_indices is not None):
             raise ValueError("TTInferenceBag: a hot row table is not served on route 'fp32' -- the twin pools inside its own forward "
                              "and hands out no rows for a compacted batch to add to the hits' sums; it needs a geometry of the "
-                             "bf16 kernels (three cores; wide=True / mfma_tail=True widen the domain)")
+                             "bf16 kernels (three cores, or four with four_cores=True; wide=True / mfma_tail=True widen the domain)")
         if self.route != "fp32":
             if cores[0].is_cuda:
-                pack = {"bf16": _engine.pack_cores_bf16, "bf16w": _engine.pack_cores_bf16w, "bf16m": _engine.pack_cores_bf16m}
+                pack = {"bf16": _engine.pack_cores_bf16, "bf16w": _engine.pack_cores_bf16w, "bf16m": _engine.pack_cores_bf16m,
+                        "bf16q": _engine.pack_cores_bf16q}
                 packed = pack[self.route](*geom, cores)
             else:
                 packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
@@ -240,16 +258,19 @@ class TTInferenceBag(nn.Module):
                 f"ranks={self.tt_ranks[1:-1]}, mode={self.mode}{hot}")
 
     def _packed(self) -> List[torch.Tensor]:
-        return [self.packed_core0, self.packed_core1, self.packed_core2]
+        return [getattr(self, f"packed_core{t}") for t in range(len(self.tt_q_shapes))]
 
     # ------------------------------------------------------------------ rows of the bf16 routes
     def _rows_hip(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor], plan=None) -> torch.Tensor:
-        rows = {"bf16": _engine.tt_rows_bf16, "bf16w": _engine.tt_rows_bf16w, "bf16m": _engine.tt_rows_bf16m}[self.route]
+        rows = {"bf16": _engine.tt_rows_bf16, "bf16w": _engine.tt_rows_bf16w, "bf16m": _engine.tt_rows_bf16m,
+                "bf16q": _engine.tt_rows_bf16q}[self.route]
         n = 1 if tableidx is None else self.num_tables
         return rows(n, self.embedding_dim, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, tableidx, self._packed(), plan)
 
     def _rows_torch(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor]) -> torch.Tensor:
         """CPU tensors (any device, really): the chain product in float32 from the packed cores"""
+        if len(self.tt_q_shapes) == 4:
+            return self._rows_torch4(flat, tableidx)
         c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
         p, q, (r1, r2) = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks[1:3]
         idx = flat.clamp(min=0)
@@ -262,6 +283,24 @@ class TTInferenceBag(nn.Module):
         c = c2[tab * p[2] + i2].view(-1, r2, q[2])
         x0 = torch.bmm(a, b).view(-1, q[0] * q[1], r2)
         return torch.bmm(x0, c).reshape(-1, self.embedding_dim)
+
+    def _rows_torch4(self, flat: torch.Tensor, tableidx: Optional[torch.Tensor]) -> torch.Tensor:
+        """four cores in chain order: (core_0 core_1) (core_2 core_3)"""
+        c0, c1, c2, c3 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks)
+        p, q, (r1, r2, r3) = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks[1:4]
+        idx = flat.clamp(min=0)
+        i3 = idx % p[3]
+        i2 = (idx // p[3]) % p[2]
+        i1 = (idx // (p[2] * p[3])) % p[1]
+        i0 = (idx // (p[1] * p[2] * p[3])).clamp(max=p[0] - 1)
+        tab = tableidx if tableidx is not None else torch.zeros_like(idx)
+        a = c0[tab * p[0] + i0].view(-1, q[0], r1)
+        b = c1[tab * p[1] + i1].view(-1, r1, q[1] * r2)
+        c = c2[tab * p[2] + i2].view(-1, r2 * q[2], r3)
+        d = c3[tab * p[3] + i3].view(-1, r3, q[3])
+        x0 = torch.bmm(a, b).view(-1, q[0] * q[1], r2)
+        m = torch.bmm(c, d).view(-1, r2, q[2] * q[3])
+        return torch.bmm(x0, m).reshape(-1, self.embedding_dim)
 
     def _bags(self, indices: torch.Tensor, offsets: Optional[torch.Tensor]):
         """the source's call forms -> (flat int64 indices, closed int64 offsets)"""

@@ -988,6 +988,47 @@ int ttx_tt_rows_bf16m(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* 
                       const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
                       ttx_stream_t stream);
 
+/* ---- bf16 inference forward, four cores (csrc/ttx_tt_bf16q.hip; not in the reference) -----------------------
+ * The same forward for FOUR-core tables, which the three kernels above refuse: all three products of the chain on
+ * mfma_f32_16x16x32_bf16 in matrix-chain order, row = (core_0 core_1) (core_2 core_3).  OPT-IN: a surface of its own; every
+ * entry point above returns exactly what it returned before it existed.
+ * SUPPORTED (ttx_tt_rows_bf16q_supported: host-side, stateless, touches no device; any p, any num_tables, p_tables or not):
+ *   T == 4, r1, r2, r3 <= 64, q0 <= 16, q1 <= 64, q3 <= 16, q2 q3 <= 32, and the bf16 x_0 and M of ONE lookup -- q0 AS + Q23P S
+ *   bytes with K2p = r2 rounded up to 32, S = 2 (K2p + 8), AS = q1 S (+ 16 where q1 is even), Q23P = q2 q3 rounded up to 16 --
+ *   plus 2 KiB of lookup records, within 160 KiB of LDS.  Everything else returns 0 here and TTX_EUNSUPPORTED from the pack and
+ *   rows calls.
+ * PACKED LAYOUT (all bf16, padding +0, K1p / K3p = r1 / r3 rounded up to 32, N1 = q1 r2, N1p = N1 rounded up to 16):
+ *   core 0   [slices][q0][K1p]       as above
+ *   core 1   [slices][N1p][K1p]      as above (transposed: column (b, k2) holds its k1 index contiguously)
+ *   core 2   [slices][r2 q2][K3p]    the natural order of the fp32 slice [r2][q2][r3], k3 padded: row (k2, c) is one A fragment
+ *   core 3   [slices][16][K3p]       TRANSPOSED: column d of the fp32 slice [r3][q3] holds its k3 index contiguously at d K3p + k3;
+ *                                    rows q3 .. 15 are zero
+ *   ttx_tt_pack_bf16q_elems / ttx_tt_pack_bf16q (t = 0 .. 3): as above, the same rounding bit for bit.
+ * ROWS  ttx_tt_rows_bf16q: arguments (packed_cores: a HOST array of 4 device pointers), plan, workspace
+ *   (ttx_tt_rows_bf16q_workspace_bytes), output order, determinism and capture as ttx_tt_rows_bf16.  One work-group of 256
+ *   threads per pivot chunk; of the plan it reads chunk_rec and lrec = {n, sid_0, sid_2, sid_3} only (not the fp32 route's merged
+ *   last cores).  A pass of SC lookups (SC q0 <= 64 and the pass's x_0 and M within 80 KiB, at least one) computes
+ *   x_0^T = (core_0 core_1)^T and M^T = (core_2 core_3)^T on the MFMA, rounds each ONCE to bf16 (nearest even) into LDS, and after
+ *   one barrier computes row^T per lookup on the MFMA (M: (c, d), N: 16 rows (a, b), K: k2); a lane stores four consecutive
+ *   (c, d) of one row (a, b).  Nothing of a lookup goes to memory except its row.
+ * NUMERICS (inputs: the bf16 cores; c_t their exact values; x_0 = c_0 c_1, M = c_2 c_3).  Against the float64 chain product on
+ *   the same cores, element by element:
+ *     |err(row[a, b, (c, d)])| <= 2^-7 sum_k2 |x_0[a, (b, k2)]| |M[k2, (c, d)]|
+ *                                 +  (r1 + r2 + r3 + 3) 2^-24 sum_{k1, k2, k3} |c_0| |c_1| |c_2| |c_3|
+ *   (first term: the two nearest-even roundings to an 8-bit significand, each with relative error <= 2^-9, together below
+ *   2^-8 + 2^-18, stated with the factor of two the three-core bound leaves for second-order terms; second: the fp32 accumulation
+ *   of the three products -- r1 and r3 additions of exact products, r2 fused multiply-adds -- to first order, with one unit of
+ *   slack).  A pooled element: the sum of its rows' bounds plus len 2^-24 sum |row|.  Rows are not bit-equal to the fp32 route's.
+ *   Cores of integers in {-1, 0, 1} give exact rows (|x_0|, |M| <= 64 are exact in bf16, |row| <= 64^3 < 2^24).
+ * ERRORS: as above, under the names pack_bf16q / tt_rows_bf16q in ttx_last_error(). */
+int ttx_tt_rows_bf16q_supported(const ttx_geom* g);
+int64_t ttx_tt_pack_bf16q_elems(const ttx_geom* g, int32_t t);
+int ttx_tt_pack_bf16q(const ttx_geom* g, int32_t t, const float* core_f32, void* packed, ttx_stream_t stream);
+size_t ttx_tt_rows_bf16q_workspace_bytes(const ttx_geom* g, int32_t D, int64_t nnz);
+int ttx_tt_rows_bf16q(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* indices, const int64_t* tableidx,
+                      const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
+                      ttx_stream_t stream);
+
 /* ---- dense rows: a range of a table expanded (csrc/ttx_tt_expand.hip; not in the reference) -------------------
  * out[n - row_begin, :] = the TT row of index n of table `table`, for row_begin <= n < row_end, from the fp32 cores in their
  * ordinary layout (cores: a HOST array of 3 device pointers, as tt_cores everywhere).  The one operation that takes no indices:
