@@ -6,6 +6,7 @@
     python examples/serve_bf16.py --mfma-tail  # D = 1024, q = [8, 8, 16]: both products on the bf16 MFMA (route "bf16m")
     python examples/serve_bf16.py --four-cores  # D = 256, q = [4, 4, 4, 4]: a four-core table on the bf16 MFMA (route "bf16q")
     python examples/serve_bf16.py --hot 4096   # keep the 4096 most visited rows of a skewed stream expanded
+    python examples/serve_bf16.py --fused-bags  # one pooled launch per call, no plan and no rows (route "bf16b")
 
 1. a dense table (low TT rank plus noise) stands in for a trained nn.EmbeddingBag;
 2. `TTEmbeddingBag.from_pretrained` factors it by TT-SVD into an ordinary module;
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--mfma-tail", action="store_true", help="a table of width 1024 (q = [8, 8, 16]) served on the MFMA-tail bf16 kernel")
     ap.add_argument("--four-cores", action="store_true", help="a four-core table of width 256 (q = [4, 4, 4, 4]) served on the four-core bf16 kernel")
     ap.add_argument("--hot", type=int, default=0, metavar="N", help="serve the N most visited rows of a Zipf 1.2 stream from a hot row table")
+    ap.add_argument("--fused-bags", action="store_true", help="serve every call as ONE pooled launch (also takes per_sample_weights / padding_idx)")
     args = ap.parse_args()
     wide, tail, four = args.wide, args.mfma_tail, args.four_cores
     import tt_embeddings_ops as ops
@@ -62,7 +64,8 @@ def main():
         idx = torch.randperm(E, device=dev)[ranks]
         rows, counts = torch.unique(idx, return_counts=True)
         hot = rows[torch.argsort(counts, descending=True)[:args.hot]]
-    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide, mfma_tail=tail, four_cores=four, hot_indices=hot)
+    served = ttx_infer.TTInferenceBag.from_module(trained, wide=wide, mfma_tail=tail, four_cores=four, hot_indices=hot,
+                                                  fused_bags=args.fused_bags)
     print(served)
     if hot is not None:
         print(f"hot rows {served.hot_rows_count}: {torch.isin(idx, hot).float().mean().item():.1%} of the batch's lookups are served from them")

@@ -242,6 +242,8 @@ def _load(path):
     L.ttx_tt_rows_bf16q_workspace_bytes.restype = C.c_size_t
     L.ttx_tt_rows_bf16q_workspace_bytes.argtypes = [G, i32, i64]
     L.ttx_tt_rows_bf16q.argtypes = [G, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.ttx_tt_bags_bf16_supported.argtypes = [G]
+    L.ttx_tt_bags_bf16.argtypes = [G, i32, i64, i64, vp, vp, vp, i64, i32, vp, vp, vp]
     L.ttx_tt_expand_supported.argtypes = [G]
     L.ttx_tt_expand.argtypes = [G, i32, i64, i64, vp, vp, vp]
     L.ttx_bag_sum_pool.argtypes = [i64, i32, vp, vp, vp, vp]
@@ -1292,6 +1294,45 @@ def tt_rows_bf16q(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, ta
     """tt_rows_bf16 for a four-core table (all three products on the bf16 MFMA, x_0 and the merged last cores in LDS) from the
     four cores of pack_cores_bf16q"""
     return _tt_rows_bf("bf16q", num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, tableidx, packed_cores, plan)
+
+
+def tt_bags_bf16_supported(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks) -> bool:
+    """does the pooled one-launch bf16 kernel take this geometry (T = 3, a shape of tt_rows_bf16m, ranks <= 64, q0 <= 16,
+    q0 q1 <= 64, q2 <= 32, one p for every table)?  Host-side: no GPU needed."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    return bool(lib().ttx_tt_bags_bf16_supported(C.byref(g)))
+
+
+def tt_bags_bf16(num_tables, D, tt_p_shapes, tt_q_shapes, tt_ranks, indices, offsets, packed_cores,
+                 per_sample_weights: Optional[torch.Tensor] = None, padding_idx: Optional[int] = None,
+                 mean: bool = False) -> torch.Tensor:
+    """pooled bags [nb, D] float32 from the packed bf16 cores of pack_cores_bf16m in ONE launch (no plan, no rows): `offsets` closed
+    ([nb + 1], the last = indices.numel()), bag b of table b // (nb // num_tables); `per_sample_weights` [nnz] float32 scale a
+    lookup's row (sum only); a slot equal to `padding_idx` is skipped and not counted for the mean."""
+    g = _geom(num_tables, tt_p_shapes, tt_q_shapes, tt_ranks)
+    dev = _dev(packed_cores[0])
+    if len(packed_cores) != 3 or any(c.dtype != torch.bfloat16 or not c.is_contiguous() or c.device != dev for c in packed_cores):
+        raise RuntimeError("tt_embeddings: tt_bags_bf16 needs the 3 packed bfloat16 cores of pack_cores_bf16m on one device")
+    lb = lib()
+    for t, c in enumerate(packed_cores):
+        if c.numel() != lb.ttx_tt_pack_bf16m_elems(C.byref(g), t):
+            raise RuntimeError(f"tt_embeddings: packed core {t} holds {c.numel()} elements, the geometry needs "
+                               f"{lb.ttx_tt_pack_bf16m_elems(C.byref(g), t)}")
+    indices, offsets = _i64(indices, "indices"), _i64(offsets, "offsets")
+    nnz, nb = indices.numel(), offsets.numel() - 1
+    if nb < 0:
+        raise RuntimeError("tt_embeddings: tt_bags_bf16: offsets must hold nb + 1 entries")
+    w = None
+    if per_sample_weights is not None:
+        w = _f32(per_sample_weights, "per_sample_weights").reshape(-1)
+        if w.numel() != nnz:
+            raise RuntimeError(f"tt_embeddings: tt_bags_bf16: {w.numel()} per_sample_weights for {nnz} indices")
+    out = torch.empty((nb, D), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(lb.ttx_tt_bags_bf16(C.byref(g), D, nb, nnz, indices.data_ptr(), offsets.data_ptr(), None if w is None else w.data_ptr(),
+                                   -1 if padding_idx is None else int(padding_idx), int(bool(mean)), _ptr_array(packed_cores),
+                                   out.data_ptr(), _stream(dev)))
+    return out
 
 
 # ---- dense rows: a range of a table expanded (include/ttx.h "dense rows"; the method on top: dense_rows of the modules) ----

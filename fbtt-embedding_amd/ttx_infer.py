@@ -26,6 +26,15 @@ order (core_0 core_1) (core_2 core_3), both factors rounded once to bf16 in LDS:
 bit-equal to the fp32 route.  Routes are tried in the order "bf16", "bf16w" (with `wide`), "bf16m" (with `mfma_tail`), "bf16q"
 (with `four_cores`), "fp32".
 
+`from_module(trained, fused_bags=True)` opts in to the POOLED one-launch kernel for a TTEmbeddingBag or
+TableBatchedTTEmbeddingBag whose geometry it takes (three cores, ranks <= 64, q0 q1 <= 64, q2 <= 32): `route == "bf16b"`, tried
+FIRST when asked for, the packed buffers of `pack_cores_bf16m`.  A call is the call-form normalisation and ONE `tt_bags_bf16`
+launch -- no prologue, no plan, no rows, no pooling launch: a wave walks a bag's lookups and sums them in its MFMA accumulators.
+Only this route serves what every source module serves and the others refuse: a source with `padding_idx` (the value is kept; such
+slots are skipped and not counted for the mean) and `forward(indices, offsets, per_sample_weights=w)` (float32, the numel of
+indices, mode "sum" only).  Within its own bound (include/ttx.h), not bit-equal to the other routes; a TTEmbedding source or a
+geometry outside the domain keeps the route it gets without the flag; a hot table with the flag is refused.
+
 `from_module(trained, hot_indices=rows)` (one 1-D int64 tensor, or one per table) keeps those rows EXPANDED beside the cores
 (DESIGN.md 4.23): computed once through the module's own route, rounded to bf16, as the buffers `hot_keys` [K] (sorted, key =
 table * num_embeddings + index) and `hot_rows` [K, D]; `hot_rows_count` is K.  A call then probes the table, pools the hits from
@@ -36,7 +45,8 @@ the hot set is what it holds cached, the hot rows are its trained `cache_weight`
 "bf16q"; the "fp32" route refuses a hot table (its twin hands out no rows).  Without either argument nothing changes.
 
 Limits: the bf16 kernels take three cores, or four with ranks <= 64 and q2 q3 <= 32 (two cores, four beyond that: "fp32"); no
-fp16 / fp8 weights; rows and output stay float32; no padding_idx, no mode="max", no per_sample_weights, a live row
+fp16 / fp8 weights; rows and output stay float32; padding_idx and per_sample_weights on route "bf16b" only, where one bag is
+one work-group (a very long bag is not split); no mode="max"; a live row
 cache only as the hot table above (which is fixed at freeze time), not the mixed-cardinality or sharded module classes (the C
 entry points do take p_tables geometries); nothing trains."""
 from typing import List, Optional, Sequence
@@ -113,7 +123,7 @@ class TTInferenceBag(nn.Module):
 
     @classmethod
     def from_module(cls, module: nn.Module, wide: bool = False, mfma_tail: bool = False, hot_indices=None,
-                    hot_from_cache: bool = False, four_cores: bool = False) -> "TTInferenceBag":
+                    hot_from_cache: bool = False, four_cores: bool = False, fused_bags: bool = False) -> "TTInferenceBag":
         if not isinstance(module, _ops.TableBatchedTTEmbeddingBag) or isinstance(module.tt_p_shapes[0], (list, tuple)) \
                 or hasattr(module, "_p_flat"):
             raise TypeError("TTInferenceBag.from_module takes a TTEmbeddingBag, a TableBatchedTTEmbeddingBag or a TTEmbedding, got "
@@ -121,7 +131,13 @@ class TTInferenceBag(nn.Module):
         mode = module.__dict__.get("mode", "sum")
         if mode == "max":
             raise ValueError("TTInferenceBag: mode='max' is not supported (the inference path pools by sum or mean)")
-        if module.__dict__.get("padding_idx") is not None:
+        fused = bool(fused_bags) and not isinstance(module, _ops.TTEmbedding) and _engine.tt_bags_bf16_supported(
+            module.num_tables, list(module.tt_p_shapes), list(module.tt_q_shapes), list(module.tt_ranks))
+        if fused and (hot_from_cache or hot_indices is not None):
+            raise ValueError("TTInferenceBag: a hot row table is not served with fused_bags=True -- the hot path is built on "
+                             "compaction and rows, the pooled kernel has neither; drop one of the two")
+        padding_idx = module.__dict__.get("padding_idx")
+        if padding_idx is not None and not fused:
             raise ValueError("TTInferenceBag: a module with padding_idx is not supported")
         live = bool(module.use_cache and not module.warmup)
         if live and not hot_from_cache:
@@ -141,7 +157,10 @@ class TTInferenceBag(nn.Module):
         self.mode, self.include_last_offset = mode, bool(module.include_last_offset)
         cores = [c.detach() for c in module.tt_cores]
         geom = (self.num_tables, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks)
-        if _engine.tt_rows_bf16_supported(*geom):
+        self.padding_idx = padding_idx  # (None on every route but "bf16b")
+        if fused:
+            self.route = "bf16b"  # (opt-in, tried first: one pooled launch, weights and padding inside the walk)
+        elif _engine.tt_rows_bf16_supported(*geom):
             self.route = "bf16"
         elif wide and _engine.tt_rows_bf16w_supported(*geom):
             self.route = "bf16w"  # (opt-in: the column-blocked kernel where the narrow one refuses)
@@ -158,10 +177,10 @@ class TTInferenceBag(nn.Module):
         if self.route != "fp32":
             if cores[0].is_cuda:
                 pack = {"bf16": _engine.pack_cores_bf16, "bf16w": _engine.pack_cores_bf16w, "bf16m": _engine.pack_cores_bf16m,
-                        "bf16q": _engine.pack_cores_bf16q}
+                        "bf16q": _engine.pack_cores_bf16q, "bf16b": _engine.pack_cores_bf16m}
                 packed = pack[self.route](*geom, cores)
             else:
-                packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
+                packed = pack_cores_torch(cores, self.tt_q_shapes, self.tt_ranks, self.route in ("bf16m", "bf16b"))
             for t, pk in enumerate(packed):
                 self.register_buffer(f"packed_core{t}", pk)
         else:
@@ -252,6 +271,25 @@ class TTInferenceBag(nn.Module):
             out = out / lens.clamp(min=1).to(torch.float32).unsqueeze(1)
         return out
 
+    def _forward_fused(self, flat: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor]) -> torch.Tensor:
+        """route "bf16b" -> [bags, D]: ONE launch on a GPU; on CPU tensors the same sum from _rows_torch, with padding dropped and
+        weights applied by torch ops"""
+        nb, D, pad = offsets.numel() - 1, self.embedding_dim, self.padding_idx
+        if flat.is_cuda:
+            return _engine.tt_bags_bf16(self.num_tables, D, self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks, flat, offsets,
+                                        self._packed(), weights, pad, self.mode == "mean")
+        lens = offsets[1:] - offsets[:-1]
+        bag = torch.repeat_interleave(torch.arange(nb, dtype=torch.int64), lens)
+        keep = flat != pad if pad is not None else torch.ones_like(flat, dtype=torch.bool)
+        rows = self._rows_torch(flat[keep], bag[keep] // (nb // self.num_tables))
+        if weights is not None:
+            rows = rows * weights[keep].unsqueeze(1)
+        out = torch.zeros((nb, D), dtype=torch.float32).index_add_(0, bag[keep], rows)
+        if self.mode == "mean":
+            live = torch.zeros(nb, dtype=torch.int64).index_add_(0, bag, keep.long())
+            out = out / live.clamp(min=1).to(torch.float32).unsqueeze(1)
+        return out
+
     def extra_repr(self) -> str:
         hot = f", hot_rows={self.hot_rows_count}" if self.hot_rows_count else ""
         return (f"{self.kind}, route={self.route}, num_tables={self.num_tables}, p={self.tt_p_shapes}, q={self.tt_q_shapes}, "
@@ -271,7 +309,7 @@ class TTInferenceBag(nn.Module):
         """CPU tensors (any device, really): the chain product in float32 from the packed cores"""
         if len(self.tt_q_shapes) == 4:
             return self._rows_torch4(flat, tableidx)
-        c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks, self.route == "bf16m")
+        c0, c1, c2 = unpack_cores_torch(self._packed(), self.tt_q_shapes, self.tt_ranks, self.route in ("bf16m", "bf16b"))
         p, q, (r1, r2) = self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks[1:3]
         idx = flat.clamp(min=0)
         i2 = (idx % p[2]).clamp(max=p[2] - 1)
@@ -319,11 +357,24 @@ class TTInferenceBag(nn.Module):
         return indices, offsets.contiguous()
 
     @torch.no_grad()
-    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """bags: 1-D indices with offsets, or [N, L] with offsets=None -> [num_tables, B, D] ([B, D] from a TTEmbeddingBag, as
-        its source returns); a TTEmbedding source: indices of any shape -> indices.shape + (D,).  float32, no grad."""
+        its source returns); a TTEmbedding source: indices of any shape -> indices.shape + (D,).  float32, no grad.
+        per_sample_weights (route "bf16b" only): float32, the numel of indices, mode "sum"."""
         if indices.dtype not in (torch.int64, torch.int32):
             raise ValueError(f"indices must be int64 or int32, got {indices.dtype}")
+        if per_sample_weights is not None:
+            if self.route != "bf16b":
+                raise ValueError("TTInferenceBag: per_sample_weights are served by from_module(..., fused_bags=True) only "
+                                 f"(route 'bf16b'); this module is on route {self.route!r}")
+            if self.mode != "sum":
+                raise ValueError(f"per_sample_weights is only supported with mode='sum' (as in torch), not mode={self.mode!r}")
+            if per_sample_weights.numel() != indices.numel():
+                raise ValueError("per_sample_weights must have the shape of indices")
+            if per_sample_weights.dtype != torch.float32:
+                raise ValueError(f"per_sample_weights must be float32, got {per_sample_weights.dtype}")
+            per_sample_weights = per_sample_weights.detach().reshape(-1).contiguous()
         D = self.embedding_dim
         if self.route == "fp32":
             out = self.fp32(indices) if self.kind == "embedding" else self.fp32(indices, offsets)
@@ -350,6 +401,8 @@ class TTInferenceBag(nn.Module):
             return torch.zeros(shape, dtype=torch.float32, device=flat.device)
         if self.hot_rows_count:
             return self._forward_hot(flat, offsets, self.num_tables).view(shape)
+        if self.route == "bf16b":
+            return self._forward_fused(flat, offsets, per_sample_weights).view(shape)
         if flat.is_cuda:
             _, tableidx, plan = _engine.lookup_prologue(flat, offsets, self.num_tables, self.tt_p_shapes, self.tt_q_shapes,
                                                         self.tt_ranks)

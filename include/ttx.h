@@ -1029,6 +1029,36 @@ int ttx_tt_rows_bf16q(const ttx_geom* g, int32_t D, int64_t nnz, const int64_t* 
                       const void* const* packed_cores, float* rows, const void* plan, void* workspace, size_t workspace_bytes,
                       ttx_stream_t stream);
 
+/* ---- bf16 inference forward, pooled in one launch (csrc/ttx_tt_bags_bf16.hip; not in the reference) ------------
+ * output[b, :] = the sum (mean != 0: the mean) of bag b's TT rows, from the packed bf16 cores of ttx_tt_pack_bf16m, in ONE launch:
+ * no plan, no sort, no workspace, no rows in memory; nothing is read back or allocated.  per_sample_weights (NULL: none) scale a
+ * lookup's row; a slot whose index equals padding_idx (-1: none) is skipped and not counted for the mean.  OPT-IN: a surface of
+ * its own; every entry point above returns exactly what it returned before it existed.
+ * SUPPORTED (ttx_tt_bags_bf16_supported: host-side, stateless, touches no device): T == 3, ttx_tt_rows_bf16m_supported(g),
+ *   r1 <= 64 and r2 <= 64, q0 <= 16, q0 q1 <= 64 (at most four 16-row tiles of product 2: the bag's accumulators stay in
+ *   registers), q2 <= 32, ONE p for every table (p_tables is refused: the kernel decodes indices itself), any num_tables.
+ *   Everything else returns 0 here and TTX_EUNSUPPORTED from ttx_tt_bags_bf16.
+ * ARGUMENTS  indices [nnz] int64; offsets [nb + 1] int64, CLOSED (offsets[nb] = nnz); bag b belongs to table b / (nb / num_tables);
+ *   per_sample_weights [nnz] float32 or NULL (not together with mean); packed_cores: a HOST array of the 3 device pointers of
+ *   ttx_tt_pack_bf16m (16-byte aligned); output [nb, D] float32 (16-byte stores where q2 % 4 == 0 and output is 16-byte aligned,
+ *   scalar stores otherwise).  An index is decoded as every lookup kernel here decodes it: negative -> 0, i0 clamped to p0 - 1;
+ *   a bag is cut to [0, nnz).  nb == 0 launches nothing.  An empty or all-padding bag gives zeros.
+ * KERNEL  one work-group of 256 threads per bag; wave w walks slots w, w + 4, .. and runs product 2 of each of its lookups into
+ *   ONE set of fp32 accumulators (x_0 is multiplied by the weight in fp32 and rounded ONCE to bf16, nearest even, in the wave's
+ *   own LDS tile); the four waves' sums are added in wave order by a fixed owner per element.  No atomics: bit-identical from run
+ *   to run, capturable.
+ * NUMERICS (inputs: the bf16 cores; w_l the weights, 1 without; live = the bag's lookups that are not padding,
+ *   L = ceil(live / 4)).  Against the float64 weighted sum on the same cores, element by element:
+ *     |err| <= 2^-8 sum_l |w_l| sum_k2 |x_0| |c_2|  +  (r1 + L r2 + 6) 2^-24 sum_l |w_l| sum_{k1, k2} |c_0| |c_1| |c_2|
+ *   (r1: x_0; L r2: one chain of L r2 fp32 multiply-adds; 1: the weight; 3: the combine; 2 of slack).  mean: both over
+ *   max(1, live), plus 2^-24 |out|.  Integer cores and weights with |x_0 w| <= 128 and |sum| < 2^24 give the exact sum.
+ * ERRORS: -1 before a device is touched for a NULL / misaligned pointer, D != prod(q), nb or nnz out of range, nb not a multiple
+ *   of num_tables, per_sample_weights together with mean; under the name tt_bags_bf16 in ttx_last_error(). */
+int ttx_tt_bags_bf16_supported(const ttx_geom* g);
+int ttx_tt_bags_bf16(const ttx_geom* g, int32_t D, int64_t nb, int64_t nnz, const int64_t* indices, const int64_t* offsets,
+                     const float* per_sample_weights, int64_t padding_idx, int32_t mean, const void* const* packed_cores,
+                     float* output, ttx_stream_t stream);
+
 /* ---- dense rows: a range of a table expanded (csrc/ttx_tt_expand.hip; not in the reference) -------------------
  * out[n - row_begin, :] = the TT row of index n of table `table`, for row_begin <= n < row_end, from the fp32 cores in their
  * ordinary layout (cores: a HOST array of 3 device pointers, as tt_cores everywhere).  The one operation that takes no indices:
